@@ -6,8 +6,15 @@ DepthDecoder, PoseDecoder) + train_loss (4 scales, warp+SSIM+L1, smoothness) + f
 gradient all-reduce over RCCL (N > 1, bucketed per backward segment and overlapped with the
 remaining backward) + Flux ADAM update.  Inputs are resident in HBM before timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (``value``,
+``ms_per_step`` = milliseconds per timed step).  ``--dump-outputs DIR`` also writes what the last
+timed step left its caller as ``DIR/<name>.npy`` (float32; the inputs are seeded, so two builds
+can be compared array for array).  ``--full`` adds the measurements that take runs of their own:
+the HIP-event roofline probe (``--no-probe`` skips it) and the CPU baseline
+(``--no-cpu-baseline`` skips it).
 
 ``--gpus N`` with N > 1 and no launcher around it (WORLD_SIZE unset) starts the N local ranks
 itself (torchrun-style, before anything touches the GPU) and exits with their status; it exits
@@ -16,10 +23,11 @@ never runs fewer ranks than asked.  The JSON line carries the communicator's own
 (md2_comm_rank) and the all-reduce calls / bytes per step it counted (md2_comm_stats).
 
 Rank 0 prints ONE JSON line.  ``value`` = images (training triplets) per second for the whole
-job; ``roofline`` is measured live with HIP events on the model's stream around every
-encoder 3x3 conv launch (fwd + dgrad + wgrad, the MFMA-bound kernels); ``roofline_photometric``
-does the same for the fused warp+SSIM kernel (HBM-bound); ``cpu_baseline`` times the CPU
-restatement (oracle/) of the same step on this host (rank 0, N = 1 only)."""
+job.  With ``--full``: ``roofline`` is measured live with HIP events on the model's stream around
+every encoder 3x3 conv launch (fwd + dgrad + wgrad, the MFMA-bound kernels);
+``roofline_photometric`` does the same for the fused warp+SSIM kernel (HBM-bound);
+``cpu_baseline`` times the CPU restatement (oracle/) of the same step on this host (rank 0,
+N = 1 only)."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +59,13 @@ def parse():
     ap.add_argument("--height", type=int, default=128)
     ap.add_argument("--width", type=int, default=416)
     ap.add_argument("--arch", type=int, default=18)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, "
+                         "disparities, poses, samples of the updated parameters and of the gradient) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure: the HIP-event roofline "
+                         "probe and the CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-probe", action="store_true", help="skip the HIP-event roofline probe")
@@ -222,6 +237,35 @@ def synthetic_batch(batch, height, width, rank, device):
     return synthetic_triplets(batch, height, width, rank * batch, device)
 
 
+DUMP_MAX_ENTRIES = 1 << 21      # per array: 8 MB of float32; at most 7 arrays are large
+
+
+def dump_outputs(path, ex, model, loss_buf):
+    """Write what the last step left its caller as ``path/<name>.npy`` (float32): the loss, the
+    disparities of every level and the poses (the executor's outputs), the updated flat
+    parameters and the flat gradient.  An array of more than DUMP_MAX_ENTRIES entries is cut to
+    that many, at sorted indices drawn once from a generator seeded with 0 (the same indices for
+    the same array size in every run)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    disps, pose = ex.outputs()
+    arrays = {"loss": loss_buf, "pose": pose, "params": model.flat, "grad": model.grad}
+    for i, d in enumerate(disps):
+        arrays[f"disp_{i}"] = d
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1) if t.numel() > DUMP_MAX_ENTRIES else t.detach()
+        if t.numel() > DUMP_MAX_ENTRIES:
+            n = t.numel()
+            if n not in picks:
+                g = torch.Generator().manual_seed(0)
+                picks[n] = torch.randperm(n, generator=g)[:DUMP_MAX_ENTRIES].sort().values
+            t = t[picks[n].to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def _host_cpu():
     """Host CPU model, logical CPU count of the machine and the CPUs this process may run on."""
     model = "unknown"
@@ -376,6 +420,9 @@ def main():
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        sys.exit(2)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start the ranks here, before this process touches the GPU
         sys.exit(launch_local(args))
@@ -492,9 +539,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     loss_val = loss_buf.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ex, model, loss_buf)   # before any further step runs
 
     prof = None
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         # the event brackets of ONE step are at the mercy of host jitter (a late launch leaves
         # its bracket open while the GPU idles) and the first profiled step also creates the
         # event pool; take each category's minimum over a few profiled steps
@@ -575,7 +624,7 @@ def main():
             ms2, flop2, n2 = prof["conv_other"]
             out["conv_other"] = {"ms_per_step": round(ms2, 4), "tflops": round(flop2 / max(ms2, 1e-9) / 1e9, 3),
                                  "launches": n2}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
             except Exception as e:  # pragma: no cover - report, never fake

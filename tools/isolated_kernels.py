@@ -1,6 +1,6 @@
 """Per-kernel-family time of the train step with every kernel on the model stream (bench.py's
 HIP-event probe steps: no side-stream overlap, so durations are the kernels' own) from a
-rocprofv3 kernel trace of `bench.py --probe-steps P`: the last P steps (one photometric launch
+rocprofv3 kernel trace of `bench.py --full --probe-steps P`: the last P steps (one photometric launch
 each) are averaged.
 
     python tools/isolated_kernels.py run_kernel_trace.csv P [top]"""

@@ -6,6 +6,6 @@ export MD2_TUNING=1   # kernel / planner knobs are honoured only with this (comm
 mkdir -p gpurun_out
 for kv in "$@"; do
   if [ "$kv" = "-" ]; then envs=""; else envs="${kv//,/ }"; fi
-  v=$(env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --steps 30 --warmup 5 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['frac'], d['conv_other']['ms_per_step'])") || exit 1
+  v=$(env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 30 --warmup 5 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['frac'], d['conv_other']['ms_per_step'])") || exit 1
   echo "$kv : $v"
 done

@@ -8,8 +8,9 @@ TAG=${1:-r01}
 STEPS=${STEPS:-10}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-BENCH="$GRAFT_REPO_ROOT/bench.py --steps $STEPS --warmup 3 --no-cpu-baseline"
+BENCH="$ROOT/bench.py --full --steps $STEPS --warmup 3 --no-cpu-baseline"
 timeout -k 10 300 python3 $BENCH > "$OUT/bench_plain.json"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- python3 $BENCH --no-probe > "$OUT/bench_trace.json"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o run --output-format csv -- python3 $BENCH --no-probe > "$OUT/bench_fetch.json"
