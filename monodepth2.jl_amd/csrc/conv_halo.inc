@@ -35,8 +35,10 @@
 
 __device__ __forceinline__ uint32_t hx_swz(uint32_t off) { return off ^ ((off >> 4) & 16u); }
 
-// DBG (timing experiments only, MD2_TUNING=1 MD2_HX_DBG=k; results wrong): bit 0 = no A loads,
-// bit 1 = no staging loads / LDS image writes, bit 2 = no MFMAs
+// DBG (timing experiments only; results wrong): bit 0 = no A loads, bit 1 = no staging loads /
+// LDS image writes, bit 2 = no MFMAs.  Only DBG = 0 is in the library; a -DMD2_TIMING_VARIANTS=1
+// build of this unit (tools/build_variant.sh) adds the variants of halo_launch, selected there
+// by MD2_TUNING=1 MD2_HX_DBG=k
 // RFL (forward only): NNlib pad_reflect(x, 1) + valid conv (the DepthDecoder blocks,
 // src/depth_decoder.jl:5): a tap leaving the image reads the mirrored row / column (y = -1 -> 1,
 // y = H -> H - 2; likewise x) -- per-lane row bases and column offsets, no extra staging.
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo3_kernel(ConvArgs a) {
   const int wq = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wq >> 2, wn = wq & 3;
   const int fi = lane & 31, fh = lane >> 5;
-  const int W = a.W, W2 = a.W + HX_PAD, H = a.H;   // W2: halo row pitch (pixels)
+  const int W = a.W, W2 = Halo3Lds::pitch(a.W), H = a.H;   // W2: halo row pitch (pixels)
   const uint32_t N = (uint32_t)a.g.N;
   const uint32_t n0 = blockIdx.x * 256u;
   const int m0 = blockIdx.y * 64;
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo3_kernel(ConvArgs a) {
   const uint32_t nlast = min(n0 + 255u, N - 1u);
   const int HR = (int)fdiv(nlast, a.fd_row) + 2 - Rf;
   const int NH = (int)fdiv(N, a.fd_row);
-  const int ZHP = HR * W2;                 // zero pixels ZHP .. ZHP + 2
+  const int ZHP = Halo3Lds::zero_px(HR, W);   // zero pixels ZHP .. ZHP + 2
 
   // zero padding columns and the zero pixels, both buffers, all three parts (never overwritten)
   for (int i = tid; i < 6 * (2 * HR + 3) * 2; i += 512) {
@@ -280,6 +282,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo3_kernel(ConvArgs a) {
   if constexpr (MODE == 0 && !RFL && !EXT) {
     if (a.bn_part) {                       // block-uniform
       constexpr int TP = 257;              // LDS row pitch (floats)
+      static_assert(64 * TP * 4 <= Halo3Lds::cap, "the statistics tile overlays the image buffers");
       float* t = reinterpret_cast<float*>(lds);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -362,7 +365,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo3s2_kernel(ConvArgs a) {
   const int wq = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wq >> 2, wn = wq & 3;
   const int fi = lane & 31, fh = lane >> 5;
-  const int W = a.Wo, W2 = a.Wo + HX_PAD, H = a.Ho;   // the dY grid (staged and iterated)
+  const int W = a.Wo, W2 = Halo3s2Lds::pitch(a.Wo), H = a.Ho;   // the dY grid (staged and iterated)
   const uint32_t N = (uint32_t)a.g.N;                  // dY grid points
   const uint32_t n0 = blockIdx.x * 128u;
   const int m0 = blockIdx.y * 64;
@@ -374,7 +377,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo3s2_kernel(ConvArgs a) {
   const uint32_t nlast = min(n0 + 127u, N - 1u);
   const int HR = (int)fdiv(nlast, a.fd_row) + 2 - Rf;
   const int NH = (int)fdiv(N, a.fd_row);
-  const int ZHP = HR * W2;
+  const int ZHP = Halo3s2Lds::zero_px(HR, W);
 
   for (int i = tid; i < 6 * (2 * HR + 3) * 2; i += 512) {
     const int half = i & 1, r = i >> 1;
@@ -553,11 +556,8 @@ __global__ __launch_bounds__(512, 1) void conv_halo3s2_kernel(ConvArgs a) {
 // bit-3 half swap every 16-lane ds_read_b128 phase hits 16 distinct bank groups for any row pitch
 // (simulated).  Reflect padding is resolved in the staging (the halo holds the mirrored pixels).
 //   MW = 1: 4 waves (one M tile x 4 row pairs), two blocks per CU; MW = 2: 8 waves, one per CU.
+//   (Tile and plane sizes H2_*: conv_lds.h.)
 // ---------------------------------------------------------------------------------------------
-constexpr int H2_TH = 8, H2_TW = 32, H2_HR = H2_TH + 2, H2_PR = H2_TW + 2;   // tile, halo rows, pitch
-constexpr int H2_PX = H2_HR * H2_PR;                                       // 340 staged pixels
-constexpr int H2_PLANE = H2_PX * 32;                                       // bytes per part plane
-
 template <int MODE, int MW, int RFL = 0, int EXT = 0>
 __global__ __launch_bounds__(256 * MW, 2 / MW) void conv_halo2d_kernel(ConvArgs a) {
   static_assert(!RFL || MODE == 0, "reflect padding: forward only");
@@ -776,21 +776,24 @@ __device__ __forceinline__ uint2 hx_tr16(const uint8_t* p) {
   return __builtin_bit_cast(uint2, v);
 }
 
-// DBG (timing experiments only, MD2_TUNING=1 MD2_WHX_DBG=k; results wrong): bit 0 = no dY loads,
-// bit 1 = no X staging loads / LDS writes, bit 2 = no MFMAs, bit 3 = no B-fragment LDS reads
+// DBG (timing experiments only; results wrong): bit 0 = no dY loads, bit 1 = no X staging loads /
+// LDS writes, bit 2 = no MFMAs, bit 3 = no B-fragment LDS reads.  Only DBG = 0 is in the library;
+// a -DMD2_TIMING_VARIANTS=1 build of this unit (tools/build_variant.sh) adds the variants of
+// whalo_launch, selected there by MD2_TUNING=1 MD2_WHX_DBG=k
 template <int ITEMS, int KS, int DBG = 0>
 __global__ __launch_bounds__(384, 3) void conv_whalo_kernel(ConvArgs a) {   // 3 waves per SIMD: two 6-wave blocks per CU (<= 168 VGPRs)
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wq = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mh = wq & 1, dyi = wq >> 1;               // filter half, kernel row kh = dyi
-  const int W = a.W, H = a.H, P = W + 2;              // halo row pitch (pixels)
+  const int W = a.W, H = a.H, P = WHaloLds::pitch(W); // halo row pitch (pixels)
   const int r = a.hx_r, rW = r * W;                   // rows per chunk, pixels per chunk
   static_assert(KS >= 4, "the X staging rides in 4 slices behind the first k-steps");
+  static_assert(KS <= WHaloLds::KS_MAX, "the k table holds 16 KS_MAX words");
   const int c0 = blockIdx.x * 32, m0 = blockIdx.y * 64;
   const int cbeg = blockIdx.z * a.hx_cper, cend = min(a.hx_nchunk, cbeg + a.hx_cper);
-  const int HR = r + 2, ZHP = HR * P;                 // zero pixels ZHP .. ZHP + 2
-  const int plane = (ZHP + 3) * 64;                   // bytes per part plane
+  const int HR = r + 2, ZHP = WHaloLds::zero_px(r, W);   // zero pixels ZHP .. ZHP + 2
+  const int plane = WHaloLds::plane(ZHP);             // bytes per part plane
   const uint32_t HW = (uint32_t)H * (uint32_t)W;
 
   // zero padding columns (x = -1, W) of every halo row and the zero pixels, 3 parts, 4 x 16 B
@@ -802,7 +805,7 @@ __global__ __launch_bounds__(384, 3) void conv_whalo_kernel(ConvArgs a) {   // 3
   }
 
   // chunk pixel k -> (row rr << 16 | halo pixel of (rr, x) for dy = 0), all-ones past the chunk
-  uint32_t* ktab = reinterpret_cast<uint32_t*>(lds + 3 * plane);
+  uint32_t* ktab = reinterpret_cast<uint32_t*>(lds + WHaloLds::ktab(plane));
   for (int k = tid; k < 16 * KS; k += 384) {
     uint32_t v = 0xffffffffu;
     if (k < rW) {
@@ -1020,153 +1023,98 @@ __global__ __launch_bounds__(384, 3) void conv_whalo_kernel(ConvArgs a) {   // 3
 #if MD2_CONV_PART == 4
 // launch (conv_impl.inc plan_halo chose the shape): grid (N / 256, M / 64, splits), 512 threads,
 // the two LDS image buffers as dynamic shared memory
-int halo_launch(int mode, const ConvArgs& a, int items, int splits, int reflect, hipStream_t st) {
-  const dim3 grid(cdiv(a.g.N, 256), a.g.M / 64, splits);
-  const size_t lds = 6 * (size_t)HX_PLANE;
-  const bool nt9 = px3_terms() == 9;
-  static const int dbg = tuning_knob("MD2_HX_DBG", 0);
-#define MD2_HX_LAUNCH(MO, NTT, IT, ...)                                                          \
-  {                                                                                              \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      MD2_HIP(hipFuncSetAttribute((const void*)conv_halo3_kernel<MO, NTT, IT __VA_OPT__(,) __VA_ARGS__>, \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));       \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((conv_halo3_kernel<MO, NTT, IT __VA_OPT__(,) __VA_ARGS__>), grid, dim3(512), lds, st, a); \
-  }
-#define MD2_HX_DBGI(MO, IT)                                                                      \
-  switch (dbg) {                                                                                 \
-    case 1: MD2_HX_LAUNCH(MO, 6, IT, 1) break;                                                   \
-    case 2: MD2_HX_LAUNCH(MO, 6, IT, 2) break;                                                   \
-    case 3: MD2_HX_LAUNCH(MO, 6, IT, 3) break;                                                   \
-    case 4: MD2_HX_LAUNCH(MO, 6, IT, 4) break;                                                   \
-    default: MD2_HX_LAUNCH(MO, 6, IT, 6) break;                                                  \
-  }
-#define MD2_HX_DBGV(MO) \
-  if (items == 1) MD2_HX_DBGI(MO, 1) else MD2_HX_DBGI(MO, 2)
-#define MD2_HX_IT(MO, NTT) \
-  if (items == 1) MD2_HX_LAUNCH(MO, NTT, 1) else MD2_HX_LAUNCH(MO, NTT, 2)
-#define MD2_HX_IT_E(NTT) \
-  if (items == 1) MD2_HX_LAUNCH(1, NTT, 1, 0, 0, 1) else MD2_HX_LAUNCH(1, NTT, 2, 0, 0, 1)
-#define MD2_HX_IT_R(NTT) \
-  if (items == 1) MD2_HX_LAUNCH(0, NTT, 1, 0, 1) else MD2_HX_LAUNCH(0, NTT, 2, 0, 1)
-#define MD2_HX_NT(MO) \
-  if (nt9) MD2_HX_IT(MO, 9) else if (dbg == 0) MD2_HX_IT(MO, 6) else MD2_HX_DBGV(MO)
-  if (mode == 0 && reflect) {
-    if (nt9) MD2_HX_IT_R(9) else MD2_HX_IT_R(6)
-  } else if (mode == 1 && a.hx_ext) {
-    if (nt9) MD2_HX_IT_E(9) else MD2_HX_IT_E(6)
-  } else if (mode == 0) MD2_HX_NT(0) else MD2_HX_NT(1)
-#undef MD2_HX_NT
-#undef MD2_HX_IT_R
-#undef MD2_HX_IT_E
+template <int MODE, int RFL, int EXT>
+static int halo_launch_as(const ConvArgs& a, int items, int splits, hipStream_t st) {
+  const dim3 grid(cdiv(a.g.N, 256), a.g.M / 64, splits), block(512);
+  const LdsSize z{Halo3Lds::need(a.W), Halo3Lds::bytes(), Halo3Lds::cap};
+  const bool one = items == 1;
+  if (px3_terms() == 9)
+    return one ? lds_launch<conv_halo3_kernel<MODE, 9, 1, 0, RFL, EXT>>(grid, block, z, st, a)
+               : lds_launch<conv_halo3_kernel<MODE, 9, 2, 0, RFL, EXT>>(grid, block, z, st, a);
+#if MD2_TIMING_VARIANTS
+  // timing-only kernels of the plain bf16x6 forms (results wrong): MD2_TUNING=1 MD2_HX_DBG=k
+  if constexpr (!RFL && !EXT) {
+    static const int dbg = tuning_knob("MD2_HX_DBG", 0);
+#define MD2_HX_DBGI(IT, D) lds_launch<conv_halo3_kernel<MODE, 6, IT, D>>(grid, block, z, st, a)
+#define MD2_HX_DBGV(D) return one ? MD2_HX_DBGI(1, D) : MD2_HX_DBGI(2, D)
+    switch (dbg) {
+      case 0: break;
+      case 1: MD2_HX_DBGV(1);
+      case 2: MD2_HX_DBGV(2);
+      case 3: MD2_HX_DBGV(3);
+      case 4: MD2_HX_DBGV(4);
+      default: MD2_HX_DBGV(6);
+    }
 #undef MD2_HX_DBGV
 #undef MD2_HX_DBGI
-#undef MD2_HX_IT
-#undef MD2_HX_LAUNCH
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
+  }
+#endif
+  return one ? lds_launch<conv_halo3_kernel<MODE, 6, 1, 0, RFL, EXT>>(grid, block, z, st, a)
+             : lds_launch<conv_halo3_kernel<MODE, 6, 2, 0, RFL, EXT>>(grid, block, z, st, a);
+}
+int halo_launch(int mode, const ConvArgs& a, int items, int splits, int reflect, hipStream_t st) {
+  if (mode == 0 && reflect) return halo_launch_as<0, 1, 0>(a, items, splits, st);
+  if (mode == 1 && a.hx_ext) return halo_launch_as<1, 0, 1>(a, items, splits, st);
+  return mode == 0 ? halo_launch_as<0, 0, 0>(a, items, splits, st) : halo_launch_as<1, 0, 0>(a, items, splits, st);
 }
 
 // stride-2 data-gradient halo kernel: grid (dY points / 128, Cin / 64, splits)
 int halo_s2_launch(const ConvArgs& a, int items, int splits, hipStream_t st) {
   const dim3 grid(cdiv(a.g.N, 128), a.g.M / 64, splits);
-  const size_t lds = 6 * (size_t)HS2_PLANE;   // 80 KB: room beside it for the side stream's blocks
-#define MD2_HS2_LAUNCH(IT)                                                                       \
-  {                                                                                              \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      MD2_HIP(hipFuncSetAttribute((const void*)conv_halo3s2_kernel<IT>,                          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));       \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((conv_halo3s2_kernel<IT>), grid, dim3(512), lds, st, a);                  \
-  }
+  const LdsSize z{Halo3s2Lds::need(a.Wo), Halo3s2Lds::bytes(), Halo3s2Lds::cap};
   MD2_CHECK_ARG(items == 1, "conv_halo3s2: one staged pixel per thread");
-  MD2_HS2_LAUNCH(1)
-#undef MD2_HS2_LAUNCH
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
+  return lds_launch<conv_halo3s2_kernel<1>>(grid, dim3(512), z, st, a);
 }
 
 // 2D-tile halo kernel (conv_impl.inc plan_halo, h.d2): grid (images x tiles, M / (32 MW), splits)
-int halo2d_launch(int mode, const ConvArgs& a, int mw, int splits, int reflect, hipStream_t st) {
+template <int MODE, int RFL, int EXT>
+static int halo2d_launch_as(const ConvArgs& a, int mw, int splits, hipStream_t st) {
   const long tiles = (long)cdiv(a.W, H2_TW) * cdiv(a.H, H2_TH);
   const dim3 grid((unsigned)(a.g.N / ((long)a.H * a.W) * tiles), a.g.M / (32 * mw), splits);
-  const size_t lds = 6 * (size_t)H2_PLANE;
-#define MD2_H2_LAUNCH(MO, MWV, ...)                                                               \
-  {                                                                                              \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      MD2_HIP(hipFuncSetAttribute((const void*)conv_halo2d_kernel<MO, MWV __VA_OPT__(,) __VA_ARGS__>, \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));       \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((conv_halo2d_kernel<MO, MWV __VA_OPT__(,) __VA_ARGS__>), grid, dim3(256 * MWV), lds, st, a); \
-  }
-  if (mode == 0 && reflect) {
-    if (mw == 1) MD2_H2_LAUNCH(0, 1, 1) else MD2_H2_LAUNCH(0, 2, 1)
-  } else if (mode == 0) {
-    if (mw == 1) MD2_H2_LAUNCH(0, 1) else MD2_H2_LAUNCH(0, 2)
-  } else if (a.hx_ext) {
-    if (mw == 1) MD2_H2_LAUNCH(1, 1, 0, 1) else MD2_H2_LAUNCH(1, 2, 0, 1)
-  } else {
-    if (mw == 1) MD2_H2_LAUNCH(1, 1) else MD2_H2_LAUNCH(1, 2)
-  }
-#undef MD2_H2_LAUNCH
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
+  const LdsSize z{Halo2dLds::need(), Halo2dLds::bytes(), Halo2dLds::cap};
+  return mw == 1 ? lds_launch<conv_halo2d_kernel<MODE, 1, RFL, EXT>>(grid, dim3(256), z, st, a)
+                 : lds_launch<conv_halo2d_kernel<MODE, 2, RFL, EXT>>(grid, dim3(512), z, st, a);
+}
+int halo2d_launch(int mode, const ConvArgs& a, int mw, int splits, int reflect, hipStream_t st) {
+  if (mode == 0) return reflect ? halo2d_launch_as<0, 1, 0>(a, mw, splits, st) : halo2d_launch_as<0, 0, 0>(a, mw, splits, st);
+  return a.hx_ext ? halo2d_launch_as<1, 0, 1>(a, mw, splits, st) : halo2d_launch_as<1, 0, 0>(a, mw, splits, st);
 }
 
 // filter-gradient halo kernel: grid (Cin / 32, Cout / 64, splits), 384 threads, LDS from the
-// chunk geometry (r rows of W pixels + 2 halo rows, W + 2 columns, 3 parts of 64 B per pixel)
-int whalo_launch(const ConvArgs& a, int items, int ksteps, int splits, hipStream_t st) {
-  const dim3 grid(a.Cin / 32, a.Cout / 64, splits);
-  const size_t lds = 3 * (size_t)(((a.hx_r + 2) * (a.W + 2) + 3) * 64) + 16 * 7 * 4;   // + k table
-  static const int dbg = tuning_knob("MD2_WHX_DBG", 0);
-#define MD2_WHX_LAUNCH1(IT, K, D)                                                                \
-  {                                                                                              \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      MD2_HIP(hipFuncSetAttribute((const void*)conv_whalo_kernel<IT, K, D>,                      \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 65536));          \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL((conv_whalo_kernel<IT, K, D>), grid, dim3(384), lds, st, a);             \
-  }
-  // timing-only variants for the layer-2 shape (3 items, 7 k-steps)
-  if (dbg && items == 3 && ksteps == 7) {
-    switch (dbg) {
-      case 1: MD2_WHX_LAUNCH1(3, 7, 1) break;
-      case 2: MD2_WHX_LAUNCH1(3, 7, 2) break;
-      case 3: MD2_WHX_LAUNCH1(3, 7, 3) break;
-      case 4: MD2_WHX_LAUNCH1(3, 7, 4) break;
-      case 8: MD2_WHX_LAUNCH1(3, 7, 8) break;
-      case 11: MD2_WHX_LAUNCH1(3, 7, 11) break;
-      default: MD2_WHX_LAUNCH1(3, 7, 12) break;
+// chunk geometry (WHaloLds: r rows of W pixels + 2 halo rows, the k table behind the planes)
+template <int ITEMS>
+static int whalo_launch_it(const ConvArgs& a, int ksteps, int splits, hipStream_t st) {
+  const dim3 grid(a.Cin / 32, a.Cout / 64, splits), block(384);
+  const LdsSize z{WHaloLds::need(a.hx_r, a.W, ksteps), WHaloLds::bytes(a.hx_r, a.W), WHaloLds::cap};
+#if MD2_TIMING_VARIANTS
+  // timing-only kernels for the layer-2 shape, 3 items and 7 k-steps (results wrong):
+  // MD2_TUNING=1 MD2_WHX_DBG=k
+  if constexpr (ITEMS == 3) {
+    static const int dbg = tuning_knob("MD2_WHX_DBG", 0);
+    if (dbg && ksteps == 7) switch (dbg) {
+      case 1: return lds_launch<conv_whalo_kernel<3, 7, 1>>(grid, block, z, st, a);
+      case 2: return lds_launch<conv_whalo_kernel<3, 7, 2>>(grid, block, z, st, a);
+      case 3: return lds_launch<conv_whalo_kernel<3, 7, 3>>(grid, block, z, st, a);
+      case 4: return lds_launch<conv_whalo_kernel<3, 7, 4>>(grid, block, z, st, a);
+      case 8: return lds_launch<conv_whalo_kernel<3, 7, 8>>(grid, block, z, st, a);
+      case 11: return lds_launch<conv_whalo_kernel<3, 7, 11>>(grid, block, z, st, a);
+      default: return lds_launch<conv_whalo_kernel<3, 7, 12>>(grid, block, z, st, a);
     }
-    MD2_LAUNCH_CHECK();
-    return MD2_OK;
   }
-#define MD2_WHX_LAUNCH(IT, K) MD2_WHX_LAUNCH1(IT, K, 0)
-#define MD2_WHX_KS(IT)                                                                           \
-  switch (ksteps) {                                                                              \
-    case 4: MD2_WHX_LAUNCH(IT, 4) break;                                                         \
-    case 5: MD2_WHX_LAUNCH(IT, 5) break;                                                         \
-    case 6: MD2_WHX_LAUNCH(IT, 6) break;                                                         \
-    default: MD2_WHX_LAUNCH(IT, 7) break;                                                        \
+#endif
+  switch (ksteps) {
+    case 4: return lds_launch<conv_whalo_kernel<ITEMS, 4>>(grid, block, z, st, a);
+    case 5: return lds_launch<conv_whalo_kernel<ITEMS, 5>>(grid, block, z, st, a);
+    case 6: return lds_launch<conv_whalo_kernel<ITEMS, 6>>(grid, block, z, st, a);
+    default: return lds_launch<conv_whalo_kernel<ITEMS, 7>>(grid, block, z, st, a);
   }
+}
+int whalo_launch(const ConvArgs& a, int items, int ksteps, int splits, hipStream_t st) {
   switch (items) {
-    case 1: MD2_WHX_KS(1) break;
-    case 2: MD2_WHX_KS(2) break;
-    case 3: MD2_WHX_KS(3) break;
-    default: MD2_WHX_KS(4) break;
+    case 1: return whalo_launch_it<1>(a, ksteps, splits, st);
+    case 2: return whalo_launch_it<2>(a, ksteps, splits, st);
+    case 3: return whalo_launch_it<3>(a, ksteps, splits, st);
+    default: return whalo_launch_it<4>(a, ksteps, splits, st);
   }
-#undef MD2_WHX_KS
-#undef MD2_WHX_LAUNCH
-#undef MD2_WHX_LAUNCH1
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
 }
 #endif

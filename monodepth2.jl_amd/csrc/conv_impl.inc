@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "conv.h"
+#include "conv_lds.h"
 #include "head.h"
 
 namespace md2 {
@@ -382,12 +383,26 @@ __device__ __forceinline__ void store_out(const TensorOut& o, int m, int img, lo
 #include "conv_px3.inc"
 #include "conv_wpx3.inc"
 
-// conv_halo3 (conv_halo.inc, its own translation unit conv_halo.hip): LDS image geometry
-constexpr int HX_PX = 736;               // halo pixels per part plane, zero pixels included (W = 104 + 2: the padded decoder grid)
-constexpr int HX_PLANE = HX_PX * 32;     // bytes per part plane (16 bf16 per pixel)
-constexpr int HX_PAD = 16;               // halo row pitch = W + HX_PAD pixels (bank-conflict free)
-constexpr int HS2_PX = 416;              // conv_halo3s2: halo pixels per part plane
-constexpr int HS2_PLANE = HS2_PX * 32;
+// Launch of a kernel whose dynamic LDS is laid out in conv_lds.h: the opt-in ceiling is set once
+// per instantiation, and a launch whose kernel would index past its allocation is refused (it
+// would compute garbage without a fault).
+struct LdsSize {
+  long need, bytes, cap;   // conv_lds.h: need(...), bytes(...), cap of the kernel's geometry
+};
+template <auto KERNEL, typename... Args>
+int lds_launch(dim3 grid, dim3 block, const LdsSize& z, hipStream_t st, const Args&... args) {
+  MD2_CHECK_ARG(z.need <= z.bytes && z.bytes <= z.cap, "conv: kernel indexes past its dynamic LDS (conv_lds.h)");
+  static bool attr = false;
+  if (!attr) {
+    MD2_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)z.cap));
+    attr = true;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, block, (size_t)z.bytes, st, args...);
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
+// the LDS-halo kernels (conv_halo.inc, its own translation unit conv_halo.hip)
 int halo_launch(int mode, const ConvArgs& a, int items, int splits, int reflect, hipStream_t st);
 int halo2d_launch(int mode, const ConvArgs& a, int mw, int splits, int reflect, hipStream_t st);
 int halo_s2_launch(const ConvArgs& a, int items, int splits, hipStream_t st);
@@ -1263,8 +1278,8 @@ HaloPlan plan_halo(const ConvShape& s, int mode) {
   if (!conv_px3_used(s, mode) || !conv_tap_major(s, mode)) return h;
   const int M = mode == 0 ? s.Cout : s.Cin, C = mode == 0 ? s.Cin : s.Cout;
   if (C % 16 || s.cin_w) return h;
-  const int hrmax = 255 / s.W + 4;                       // halo rows of 256 consecutive pixels
-  const bool flat = M % 64 == 0 && hrmax * (s.W + HX_PAD) + 3 <= HX_PX && cdiv((long)hrmax * s.W, 512) <= 2;
+  const int hrmax = Halo3Lds::rows(s.W);                 // halo rows of 256 consecutive pixels
+  const bool flat = M % 64 == 0 && Halo3Lds::fits(s.W) && cdiv((long)hrmax * s.W, 512) <= 2;
   // otherwise the 2D-tile kernel (maps too wide for the flattened image, 32-row M tiles;
   // bf16x6 only).  MD2_HALO2D (MD2_TUNING=1): bit 0 forward (default), bit 1 data gradient --
   // the reflect dgrad on it (the padded 66 x 210 grid in 8 x 32 tiles + the fold) measured
@@ -1306,8 +1321,7 @@ HaloS2Plan plan_halo_s2(const ConvShape& s) {
   if (!on || s.KH != 3 || s.KW != 3 || s.stride != 2 || s.pad != 1 || s.reflect || s.cin_w) return h;
   if (s.H != 2 * s.Ho || s.W != 2 * s.Wo || s.Cin % 64 || s.Cout % 16) return h;
   if (!conv_px3_used(s, 1) || !conv_tap_major(s, 1) || tuning_knob("MD2_PX3_TERMS", 6) == 9) return h;
-  const int hrmax = 127 / s.Wo + 4;                       // halo rows of 128 consecutive points
-  if (hrmax * (s.Wo + HX_PAD) + 3 > HS2_PX) return h;    // (then <= 413 staged pixels: one per thread)
+  if (!Halo3s2Lds::fits(s.Wo)) return h;                 // (then <= 413 staged pixels: one per thread)
   h.items = 1;
   const long tiles = (long)(s.Cin / 64) * cdiv((long)s.N * s.Ho * s.Wo, 128);
   const int nch = s.Cout / 16;
@@ -1339,7 +1353,7 @@ WHaloPlan plan_whalo(const ConvShape& s, int c0) {
   // (16-byte dY loads of 4-pixel groups: chunk starts and image planes on 4-float boundaries)
   // (and 4..7 16-pixel k-steps per chunk: the X staging rides behind the first four)
   if (r == 0 || (r * s.W) % 4 || (s.H * s.W) % 4 || r * s.W < 49) return h;
-  if (3L * (((r + 2) * (s.W + 2) + 3) * 64) + 448 > 65536) return h;
+  if (!WHaloLds::fits(r, s.W)) return h;
   // (4 staged items -- layer 1's 104-wide rows -- take 198 VGPRs, one 6-wave block per CU: 91 vs
   // 81 us against conv_wgrad_px3 until the staging loads' per-lane soffset (a waterfall loop) was
   // moved into the voffset; since then 77 vs 88 us, the step 6.145 vs 6.205 ms;

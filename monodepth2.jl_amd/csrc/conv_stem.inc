@@ -126,9 +126,10 @@ __device__ __forceinline__ void stem_item(u32x4_t (&fb)[2][2][3], const uint8_t*
 // is split and written into the slot the current row no longer reads.  8 waves: wave w holds
 // filters 16 (w & 3) .. + 15 and takes every other 16-pixel subtile of a row (the parity
 // alternates with the row, so the two waves of a filter quarter share the odd subtile count).
-// FL: timing-only builds (MD2_TUNING=1 MD2_STEM_DBG=k, results wrong):
-// bit 1 = no MFMAs, bit 2 = no output stores, bit 3 = no per-row staging; bit 4 (a valid result):
-// no scheduling barrier in the K-steps
+// FL: timing-only kernels (results wrong): bit 1 = no MFMAs, bit 2 = no output stores, bit 3 = no
+// per-row staging; bit 4 (a valid result): no scheduling barrier in the K-steps.  Only FL = 0 is
+// in the library; a -DMD2_TIMING_VARIANTS=1 build of this unit (tools/build_variant.sh) adds the
+// variants of stem_s2d_launch, selected there by MD2_TUNING=1 MD2_STEM_DBG=k
 template <int FL>
 __global__ __launch_bounds__(512, 1) void conv_stem_s2d_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(512, 1) void conv_stem_s2d_kernel(ConvArgs a) {
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fq = wv & 3, sp = wv >> 2;
   const int Ho = a.Ho, Wo = a.Wo, W = a.W;
-  const int P = Wo + 3;                                  // records per s2d row (columns -2 .. Wo)
-  const uint32_t plane = (uint32_t)(5 * P * 32);         // bytes per part plane (5 ring slots)
+  const int P = StemLds::pitch(Wo);                      // records per s2d row (columns -2 .. Wo)
+  const uint32_t plane = (uint32_t)StemLds::plane(P);    // bytes per part plane (5 ring slots)
   const uint32_t NR = (uint32_t)(a.g.N / Wo);            // output rows of all images
   const uint32_t nb = gridDim.x, b = blockIdx.x;
   const uint32_t L0 = (uint32_t)((uint64_t)b * NR / nb), L1 = (uint32_t)((uint64_t)(b + 1) * NR / nb);
@@ -305,8 +306,10 @@ __device__ __forceinline__ void stem_wquad(int T, int p, int& dY, int& dX, int& 
   }
 }
 
-// DBG (timing only, MD2_TUNING=1 MD2_WSTEM_DBG=k; results wrong): bit 0 no MFMAs, bit 1 no dY
-// loads, bit 2 no transposed B reads, bit 3 no per-row staging
+// DBG (timing only; results wrong): bit 0 no MFMAs, bit 1 no dY loads, bit 2 no transposed B
+// reads, bit 3 no per-row staging.  Only DBG = 0 is in the library; a -DMD2_TIMING_VARIANTS=1
+// build of this unit (tools/build_variant.sh) adds the variants of stem_wgrad_s2d_launch,
+// selected there by MD2_TUNING=1 MD2_WSTEM_DBG=k
 template <int DBG = 0>
 __global__ __launch_bounds__(512, 1) void conv_wgrad_stem_s2d_kernel(ConvArgs a, int P) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -314,7 +317,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_stem_s2d_kernel(ConvArgs a,
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mt = wv & 3, sp = wv >> 2;                  // filter quarter, K-step parity
   const int Ho = a.Ho, Wo = a.Wo, W = a.W;
-  const uint32_t plane = (uint32_t)(5 * P * 32);
+  const uint32_t plane = (uint32_t)StemWgradLds::plane(P);
   const uint32_t NR = (uint32_t)((long)a.g.K / Wo);      // output rows of all images
   const uint32_t nb = gridDim.x, b = blockIdx.x;
   const uint32_t L0 = (uint32_t)((uint64_t)b * NR / nb), L1 = (uint32_t)((uint64_t)(b + 1) * NR / nb);
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_stem_s2d_kernel(ConvArgs a,
   // tiles, so each dY fragment is loaded and split once (two waves splitting tile halves loaded and
   // split every fragment twice); their partial sums meet in LDS at the end.
   const int p4 = lane & 3, q4 = (lane >> 2) & 3, g = lane >> 4, n = lane & 15;
-  constexpr int NT = 13;
+  constexpr int NT = StemWgradLds::TILES;
   int tdy[NT];
   uint32_t tcol[NT];
 #pragma unroll
@@ -477,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_stem_s2d_kernel(ConvArgs a,
 
   // ---- the odd-K-step waves' sums through LDS (the ring is free after the last barrier), added
   // by the even ones: (c0 + c1)_even + (c0 + c1)_odd, a fixed order
-  float* red = reinterpret_cast<float*>(lds) + (mt * NT * 4) * 64 + lane;
+  float* red = reinterpret_cast<float*>(lds) + mt * StemWgradLds::red_quarter + lane;
   if (sp == 1) {
 #pragma unroll
     for (int i = 0; i < NT; ++i)
@@ -510,7 +513,7 @@ bool stem_s2d_applies(const ConvShape& s, const TensorIn& x, const TensorOut& y)
   if (!on || s.KH != 7 || s.KW != 7 || s.stride != 2 || s.pad != 3 || s.reflect || s.Cin != 3 || s.Cout != 64) return false;
   if (s.cin_w && s.cin_w != 3) return false;
   if (s.H % 2 || s.W % 2 || s.Wo % 16 || s.Ho != s.H / 2 || s.Wo != s.W / 2) return false;
-  if (3L * 5 * (s.Wo + 3) * 32 > 163840) return false;   // the LDS ring (Wo <= 338: <= 21 subtiles per row)
+  if (!StemLds::fits(s.Wo)) return false;                // the LDS ring (Wo <= 338: <= 21 subtiles per row)
   if (x.p1 || x.c0 < s.Cin) return false;
   if (y.bias || y.act != ACT_NONE || y.accumulate || y.c0 < s.Cout) return false;
   return (long)s.N * s.Ho * s.Wo < (1L << 31);
@@ -520,70 +523,49 @@ bool stem_s2d_applies(const ConvShape& s, const TensorIn& x, const TensorOut& y)
 static int stem_blocks(const ConvShape& s) { return (int)std::min<long>(256, (long)s.N * s.Ho); }
 
 
-// the filter-gradient kernel: the forward's conditions on the input; ring pitch P a multiple of
-// 8 records covering round_up(Wo, 32) + 3 columns
-static int stem_wgrad_pitch(const ConvShape& s) { return (int)round_up(round_up(s.Wo, 32) + 3, 8); }
+// the filter-gradient kernel: the forward's conditions on the input and its own ring
+// (StemWgradLds: the pitch P, the combine buffer over the ring)
 bool stem_wgrad_s2d_applies(const ConvShape& s, const TensorIn& x) {
   static const int on = env_int("MD2_WSTEM_S2D", 1);
   TensorOut y;
   if (!on || !stem_s2d_applies(s, x, y)) return false;
-  return stem_wgrad_pitch(s) <= 512 && 15L * stem_wgrad_pitch(s) * 32 <= 163840 &&
-         (long)s.N * s.Cout * s.Ho * s.Wo * 4 < (long)OOB;
+  return StemWgradLds::fits(s.Wo) && (long)s.N * s.Cout * s.Ho * s.Wo * 4 < (long)OOB;
 }
 int stem_wgrad_blocks(const ConvShape& s) { return stem_blocks(s); }
 int stem_wgrad_s2d_launch(const ConvShape& s, const ConvArgs& a, hipStream_t st) {
-  const int P = stem_wgrad_pitch(s);
-  // the ring, or the 4 x 13 x 4 x 64 floats of the K-step-parity combine if larger
-  const size_t lds = std::max(15 * (size_t)P * 32, (size_t)4 * 13 * 4 * 64 * 4);
-  static const int dbg = tuning_knob("MD2_WSTEM_DBG", 0);
-#define MD2_WS_L(D)                                                                              \
-  {                                                                                              \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      MD2_HIP(hipFuncSetAttribute((const void*)conv_wgrad_stem_s2d_kernel<D>,                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 163840));         \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL(conv_wgrad_stem_s2d_kernel<D>, dim3(stem_blocks(s)), dim3(512), lds, st, a, P); \
-  }
+  const int P = StemWgradLds::pitch(s.Wo);
+  const dim3 grid(stem_blocks(s)), block(512);
+  const LdsSize z{StemWgradLds::need(P), StemWgradLds::bytes(P), StemWgradLds::cap};
+#if MD2_TIMING_VARIANTS
+  static const int dbg = tuning_knob("MD2_WSTEM_DBG", 0);   // MD2_TUNING=1; results wrong
   switch (dbg) {
-    case 1: MD2_WS_L(1) break;
-    case 2: MD2_WS_L(2) break;
-    case 4: MD2_WS_L(4) break;
-    case 6: MD2_WS_L(6) break;
-    case 7: MD2_WS_L(7) break;
-    case 15: MD2_WS_L(15) break;
-    default: MD2_WS_L(0) break;
+    case 1: return lds_launch<conv_wgrad_stem_s2d_kernel<1>>(grid, block, z, st, a, P);
+    case 2: return lds_launch<conv_wgrad_stem_s2d_kernel<2>>(grid, block, z, st, a, P);
+    case 4: return lds_launch<conv_wgrad_stem_s2d_kernel<4>>(grid, block, z, st, a, P);
+    case 6: return lds_launch<conv_wgrad_stem_s2d_kernel<6>>(grid, block, z, st, a, P);
+    case 7: return lds_launch<conv_wgrad_stem_s2d_kernel<7>>(grid, block, z, st, a, P);
+    case 15: return lds_launch<conv_wgrad_stem_s2d_kernel<15>>(grid, block, z, st, a, P);
+    default: break;
   }
-#undef MD2_WS_L
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
+#endif
+  return lds_launch<conv_wgrad_stem_s2d_kernel<0>>(grid, block, z, st, a, P);
 }
 
 int stem_s2d_launch(const ConvShape& s, const ConvArgs& a, hipStream_t st) {
-  const size_t lds = 3 * (size_t)(5 * (a.Wo + 3) * 32);
-  const int nb = stem_blocks(s);
-  static const int dbg = tuning_knob("MD2_STEM_DBG", 0);
-#define MD2_STEM_L(F)                                                                            \
-  {                                                                                              \
-    static bool attr = false;                                                                    \
-    if (!attr) {                                                                                 \
-      MD2_HIP(hipFuncSetAttribute((const void*)conv_stem_s2d_kernel<F>,                         \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 163840));         \
-      attr = true;                                                                               \
-    }                                                                                            \
-    hipLaunchKernelGGL(conv_stem_s2d_kernel<F>, dim3(nb), dim3(512), lds, st, a);               \
-  }
+  const int P = StemLds::pitch(a.Wo);
+  const dim3 grid(stem_blocks(s)), block(512);
+  const LdsSize z{StemLds::need(P), StemLds::bytes(P), StemLds::cap};
+#if MD2_TIMING_VARIANTS
+  static const int dbg = tuning_knob("MD2_STEM_DBG", 0);    // MD2_TUNING=1; results wrong but 16
   switch (dbg) {
-    case 2: MD2_STEM_L(2) break;
-    case 4: MD2_STEM_L(4) break;
-    case 8: MD2_STEM_L(8) break;
-    case 14: MD2_STEM_L(14) break;
-    case 16: MD2_STEM_L(16) break;
-    default: MD2_STEM_L(0) break;
+    case 2: return lds_launch<conv_stem_s2d_kernel<2>>(grid, block, z, st, a);
+    case 4: return lds_launch<conv_stem_s2d_kernel<4>>(grid, block, z, st, a);
+    case 8: return lds_launch<conv_stem_s2d_kernel<8>>(grid, block, z, st, a);
+    case 14: return lds_launch<conv_stem_s2d_kernel<14>>(grid, block, z, st, a);
+    case 16: return lds_launch<conv_stem_s2d_kernel<16>>(grid, block, z, st, a);
+    default: break;
   }
-#undef MD2_STEM_L
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
+#endif
+  return lds_launch<conv_stem_s2d_kernel<0>>(grid, block, z, st, a);
 }
 #endif
