@@ -475,6 +475,30 @@ int md2_model_debug_tensor(md2_model* m, int index, const char** name, const voi
 int md2_model_eval_disparity(md2_model* m, const float* x, int n, const float** disp,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * BatchNorm running statistics as model state, and test mode (Flux testmode!).
+ * Every train-mode forward moves the running mean / variance of each BatchNorm (Flux: momentum
+ * 0.1, variance with the m/(m-1) correction; initial state 0 / 1).  They form ONE flat fp32 vector:
+ * per BatchNorm, in the order of its gamma entry in md2_arch_param_info, C means then C variances
+ * (n_elems = 2 * sum of C).  get / set take device pointers and join pending ADAM segments like
+ * md2_model_get_params; set refuses a negative variance or a non-finite entry with MD2_EINVAL
+ * (checked on the device; the state is then unchanged).
+ * md2_model_set_testmode(m, 1): md2_model_eval_disparity and md2_model_forward normalise with the
+ * running statistics (which they no longer modify), each BatchNorm folded into the conv before it
+ * (w' = w * s, bias t; s = gamma / sqrt(var + 1e-5), t = beta - mean * s); a sample's result no
+ * longer depends on the rest of its batch.  Every training entry point (forward_loss,
+ * set_cotangents, backward_*, adam*, train_step*, loss_cotangent) returns MD2_ESTATE until
+ * md2_model_set_testmode(m, 0), which restores the train-mode state exactly (the train-mode packed
+ * weights are never overwritten; the folded packs are a second set, allocated at the first switch
+ * and counted in md2_model_device_bytes from then on).  md2_model_repack, md2_model_set_params and
+ * md2_model_set_bn_stats re-fold while test mode is on.
+ * ---------------------------------------------------------------------------------------- */
+int md2_arch_bn_stat_count(const md2_model_cfg* cfg, long long* n_bn, long long* n_elems);
+int md2_model_get_bn_stats(md2_model* m, float* out, void* stream);
+int md2_model_set_bn_stats(md2_model* m, const float* in, void* stream);
+int md2_model_set_testmode(md2_model* m, int on, void* stream);
+int md2_model_testmode(md2_model* m);
+
 #ifdef __cplusplus
 }
 #endif

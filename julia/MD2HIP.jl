@@ -178,7 +178,8 @@ end
 The HIP model of a reference `Model(encoder, depth_decoder, pose_decoder)` (src/model.jl:24-29,
 built as in scripts/script.jl:77-81) for one `TrainCache` / `Params`: the architecture (ResNet
 depth, input channels, `scale_levels`, `embedding_levels`) is read off the Flux model and its
-parameters are copied (conv kernels flipped into the library layout) into the flat θ.
+parameters are copied (conv kernels flipped into the library layout) into the flat θ, and every
+BatchNorm's running μ / σ² into the library's statistics (`set_bn_stats!`).
 """
 function HIPModel(model, cache, params; num_bins=32)
     enc, dec = model.encoder, model.depth_decoder
@@ -191,7 +192,9 @@ function HIPModel(model, cache, params; num_bins=32)
         cfg = ModelCfg(arch, in_ch, levels, params, cache; embedding_levels=emb,
                        num_bins=emb > 0 ? num_bins : 1)
         param_count(cfg)[1] == length(ps) || continue
-        return HIPModel(cfg, flat_params(cfg, ps))
+        m = HIPModel(cfg, flat_params(cfg, ps))
+        # the BatchNorm running statistics (μ, σ²) are model state too: Flux.params holds γ and β only
+        return set_bn_stats!(m, flat_bn_stats(cfg, model))
     end
     error("HIPModel: the Flux model matches no ResidualNetwork(18/34/50) + DepthDecoder + PoseDecoder table")
 end
@@ -400,6 +403,75 @@ function get_params(m::HIPModel)
                 m.handle, flux, stream_ptr()))
     return flux
 end
+
+# ------------------------------------------------------------------------------------------------
+# BatchNorm running statistics and test mode.  Flux keeps μ / σ² in the BatchNorm layers (not in
+# Flux.params); the library keeps them as one flat vector: per BatchNorm, in the order of its
+# gamma entry in the parameter table, C means then C variances (md2_model_get_bn_stats).
+# ------------------------------------------------------------------------------------------------
+function bn_stat_count(cfg::ModelCfg)
+    nb, nel = Ref{Clonglong}(), Ref{Clonglong}()
+    check(ccall((:md2_arch_bn_stat_count, lib), Cint, (Ref{ModelCfg}, Ref{Clonglong}, Ref{Clonglong}),
+                cfg, nb, nel))
+    return Int(nb[]), Int(nel[])
+end
+
+function bn_stats(m::HIPModel)
+    v = ROCVector{Float32}(undef, bn_stat_count(m.cfg)[2])
+    check(ccall((:md2_model_get_bn_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}),
+                m.handle, v, stream_ptr()))
+    return v
+end
+
+# a negative variance or a non-finite entry is refused (MD2_EINVAL; the model's state is unchanged)
+function set_bn_stats!(m::HIPModel, v::ROCVector{Float32})
+    length(v) == bn_stat_count(m.cfg)[2] || error("set_bn_stats!: $(length(v)) elements, the model needs ",
+                                                   bn_stat_count(m.cfg)[2])
+    check(ccall((:md2_model_set_bn_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}),
+                m.handle, v, stream_ptr()))
+    return m
+end
+
+# the BatchNorm layers of a Flux model in Flux.params order (the same depth-first walk over
+# Flux.trainable that params! does), i.e. the order of the table's gamma entries
+function batchnorms!(out, x)
+    x isa Flux.BatchNorm && return push!(out, x)
+    x isa AbstractArray{<:Number} && return out
+    for c in Flux.trainable(x)
+        batchnorms!(out, c)
+    end
+    return out
+end
+
+# μ / σ² of every Flux BatchNorm of `model` as the library's flat vector
+function flat_bn_stats(cfg::ModelCfg, model)
+    bns = batchnorms!(Any[], model)
+    nb, nel = bn_stat_count(cfg)
+    length(bns) == nb || error("Flux model has $(length(bns)) BatchNorm layers, the table has $nb")
+    flat = Float32[]
+    for b in bns
+        append!(flat, Array{Float32}(b.μ)); append!(flat, Array{Float32}(b.σ²))
+    end
+    length(flat) == nel || error("BatchNorm statistics: $(length(flat)) elements, the table has $nel")
+    return ROCVector{Float32}(flat)
+end
+
+"""
+    testmode!(m::HIPModel, on=true); trainmode!(m)
+
+Flux `testmode!` / `trainmode!` on the HIP path.  While on, `eval_disparity(m, x)` and
+`m(x, source_ids, target_id)` normalise with the running statistics (each BatchNorm folded into the
+conv before it; the statistics are not modified) and every training call fails with MD2_ESTATE.
+If m.θ was changed in place since the last pack, the switch re-packs (and so folds the new weights).
+"""
+function testmode!(m::HIPModel, on=true)
+    on && !m.packed && repack!(m)
+    check(ccall((:md2_model_set_testmode, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                m.handle, on ? 1 : 0, stream_ptr()))
+    return m
+end
+trainmode!(m::HIPModel) = testmode!(m, false)
+istestmode(m::HIPModel) = ccall((:md2_model_testmode, lib), Cint, (Ptr{Cvoid},), m.handle) != 0
 
 # update!(ADAM(η), θ, ∇θ) -- Flux ADAM, β = (0.9, 0.999), ε = 1e-8 (scripts/script.jl:85)
 function update!(m::HIPModel, η; β=(0.9f0, 0.999f0), ϵ=1f-8, grad_scale=1f0)

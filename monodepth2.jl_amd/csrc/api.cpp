@@ -599,4 +599,33 @@ int md2_model_eval_disparity(md2_model* m, const float* x, int n, const float** 
   return MD2_OK;
 }
 
+int md2_arch_bn_stat_count(const md2_model_cfg* cfg, long long* n_bn, long long* n_elems) {
+  MD2_CHECK_ARG(cfg != nullptr, "cfg");
+  MD2_CHECK_ARG(cfg->embedding_levels >= 0, "embedding_levels >= 0");
+  MD2_CHECK_ARG(cfg->arch == 18 || cfg->arch == 34 || cfg->arch == 50, "arch 18/34/50");
+  MD2_TRY(check_scale_levels(to_arch(cfg)));
+  long nb = 0, ne = 0;
+  MD2_TRY(arch_bn_stat_count(to_arch(cfg), &nb, &ne));
+  if (n_bn) *n_bn = nb;
+  if (n_elems) *n_elems = ne;
+  return MD2_OK;
+}
+
+int md2_model_get_bn_stats(md2_model* m, float* out, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_get_bn_stats(m->impl, out, (hipStream_t)stream);
+}
+
+int md2_model_set_bn_stats(md2_model* m, const float* in, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_set_bn_stats(m->impl, in, (hipStream_t)stream);
+}
+
+int md2_model_set_testmode(md2_model* m, int on, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_set_testmode(m->impl, on, (hipStream_t)stream);
+}
+
+int md2_model_testmode(md2_model* m) { return m ? model_testmode(m->impl) : 0; }
+
 }  // extern "C"

@@ -9,6 +9,7 @@
 //     oracle/md2_oracle.py param_spec; conv weights are re-packed K-major after each update.
 #include "model.h"
 #include "head.h"
+#include "testmode.h"
 
 #include <algorithm>
 #include <cmath>
@@ -184,6 +185,7 @@ struct RConv {
   ConvShape s{};          // N filled per call
   float* wpf = nullptr;   // packed forward weights
   float* wpd = nullptr;   // packed dgrad weights
+  float* wpt = nullptr;   // test mode: packed forward weights of the BatchNorm-folded copy
   int cat = PROF_CONV_OTHER;
 };
 struct RBN {
@@ -191,6 +193,7 @@ struct RBN {
   float *mean = nullptr, *invstd = nullptr, *rmean = nullptr, *rvar = nullptr;
   const double* part = nullptr;   // statistics partials of the current forward (bn_fwd)
   int parts = 0;
+  float *ts = nullptr, *tt = nullptr;   // test mode: the folded affine map (s, t)
 };
 struct EncStage {
   RConv conv;
@@ -448,12 +451,21 @@ class Model {
     ws_need = std::max(ws_need, conv_wgrad_workspace(s));
     if (dgrad) ws_need = std::max(ws_need, conv_dgrad_workspace(s));
   }
+  // Running statistics of every BatchNorm in ONE flat vector (the layout of
+  // md2_model_get_bn_stats: per BatchNorm C means then C variances, in the order of the gamma
+  // entries of the parameter table -- the order make_bn is called in)
+  float* bn_stats = nullptr;
+  BNStatLayout bn_layout{};
+  int* bn_flag = nullptr;       // device flag of the set_bn_stats check
   int make_bn(RBN& r, const PBN& p) {
     r.p = p;
     MD2_TRY(alloc(&r.mean, p.c));
     MD2_TRY(alloc(&r.invstd, p.c));
-    MD2_TRY(alloc(&r.rmean, p.c));
-    MD2_TRY(alloc(&r.rvar, p.c));
+    MD2_CHECK_ARG(bn_layout.n < MAX_BN, "make_bn: too many BatchNorm layers");
+    r.rmean = bn_stats + bn_layout.off[bn_layout.n];
+    r.rvar = r.rmean + p.c;
+    bn_layout.off[bn_layout.n + 1] = bn_layout.off[bn_layout.n] + 2 * p.c;
+    ++bn_layout.n;
     MD2_HIP(hipMemset(r.rmean, 0, p.c * sizeof(float)));
     std::vector<float> ones(p.c, 1.f);
     MD2_HIP(hipMemcpy(r.rvar, ones.data(), p.c * sizeof(float), hipMemcpyHostToDevice));
@@ -478,6 +490,15 @@ class Model {
       bnmax = std::max(bnmax, (long)Cc * ((B * HW + 255) / 256) * 2);   // per-tile epilogue partials
     };
     // ---- encoder
+    {
+      long nst = 0;
+      for (auto& e : spec.table)
+        if (e.name.size() > 6 && e.name.compare(e.name.size() - 6, 6, ".gamma") == 0) nst += 2 * e.numel;
+      MD2_TRY(alloc(&bn_stats, nst));
+      float* q;
+      MD2_TRY(alloc(&q, 16));
+      bn_flag = (int*)q;
+    }
     MD2_TRY(make_conv(stem, spec.stem, cfg.H, cfg.W, false, wsn));
     need_ws(stem, B, wsn, false);
     MD2_TRY(make_bn(stem_bn, spec.stem_bn));
@@ -988,6 +1009,148 @@ class Model {
     return s;
   }
 
+  // -------------------------------------------------------------------------------------------
+  // Test mode (Flux testmode!, md2_model_set_testmode): BatchNorm on the running statistics.  Each
+  // encoder BatchNorm is folded into the conv before it -- a scratch copy of the encoder's conv
+  // weights scaled by s (bn_fold_batch, which also writes the t vectors), packed by the unchanged
+  // conv_pack_batch into a SECOND set of forward packs (wpt); the train-mode packs are never
+  // written.  The stem keeps its space-to-depth kernel (no bias operand): its (s, t) are applied by
+  // affine_relu_maxpool.  Everything is allocated at the first switch to test mode.
+  bool testmode = false;
+  float* wfold = nullptr;       // [spec.depth_begin]: folded conv weights at their parameter offsets
+  float* tm_st = nullptr;       // (s, t) of every BatchNorm, laid out like bn_stats
+  FoldJob* fold_jobs = nullptr;
+  int fold_njobs = 0;
+  long fold_blocks = 0;
+  PackJob* tm_pack_jobs = nullptr;
+  int tm_pack_njobs = 0;
+  long tm_pack_blocks = 0;
+
+  int testmode_alloc() {
+    if (wfold) return MD2_OK;
+    MD2_TRY(alloc(&wfold, spec.depth_begin));
+    MD2_TRY(alloc(&tm_st, bn_layout.off[bn_layout.n]));
+    std::vector<FoldJob> fj;
+    std::vector<PackJob> pj;
+    int k = 0;
+    auto job = [&](RConv* c, RBN& bn) -> int {
+      bn.ts = tm_st + bn_layout.off[k++];
+      bn.tt = bn.ts + bn.p.c;
+      FoldJob j;
+      j.gamma = P(bn.p.g); j.beta = P(bn.p.b);
+      j.mean = bn.rmean; j.var = bn.rvar;
+      j.s = bn.ts; j.t = bn.tt;
+      j.Cout = bn.p.c;
+      if (c) {
+        const long per = (long)c->p.cin * c->p.k * c->p.k;
+        MD2_CHECK_ARG(per % 4 == 0 && c->p.cout == bn.p.c, "test mode: conv weight rows of 4n floats");
+        j.w = params + c->p.w;
+        j.wf = wfold + c->p.w;
+        j.per4 = (int)(per / 4);
+        MD2_TRY(alloc(&c->wpt, conv_fwd_packed_elems(c->s)));
+        MD2_HIP(hipMemset(c->wpt, 0, conv_fwd_packed_elems(c->s) * sizeof(float)));
+        pj.push_back(conv_pack_job(c->s, j.wf, c->wpt, nullptr));
+      }
+      fj.push_back(j);
+      return MD2_OK;
+    };
+    MD2_TRY(job(nullptr, stem_bn));
+    for (auto& sg : stages)
+      for (auto& b : sg) {
+        for (auto& e : b.st) MD2_TRY(job(&e.conv, e.bn));
+        if (b.down) MD2_TRY(job(&b.dconv, b.dbn));
+      }
+    fold_blocks = 0;
+    for (auto& j : fj) {
+      j.block_begin = fold_blocks;
+      fold_blocks += bn_fold_job_blocks(j);
+    }
+    tm_pack_blocks = 0;
+    for (auto& j : pj) {
+      j.block_begin = tm_pack_blocks;
+      tm_pack_blocks += conv_pack_job_blocks(j);
+    }
+    void* q = nullptr;
+    MD2_HIP(hipMalloc(&q, fj.size() * sizeof(FoldJob)));
+    allocs.push_back(q);
+    bytes += fj.size() * sizeof(FoldJob);
+    MD2_HIP(hipMemcpy(q, fj.data(), fj.size() * sizeof(FoldJob), hipMemcpyHostToDevice));
+    fold_jobs = (FoldJob*)q;
+    fold_njobs = (int)fj.size();
+    MD2_HIP(hipMalloc(&q, pj.size() * sizeof(PackJob)));
+    allocs.push_back(q);
+    bytes += pj.size() * sizeof(PackJob);
+    MD2_HIP(hipMemcpy(q, pj.data(), pj.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+    tm_pack_jobs = (PackJob*)q;
+    tm_pack_njobs = (int)pj.size();
+    return MD2_OK;
+  }
+  // (s, t) and the folded packs from the current parameters and running statistics
+  int refold(hipStream_t st) {
+    MD2_TRY(bn_fold_batch(fold_jobs, fold_njobs, fold_blocks, 1e-5, st));
+    return conv_pack_batch(tm_pack_jobs, tm_pack_njobs, tm_pack_blocks, st);
+  }
+  // a folded conv: bias t, ReLU where one follows directly
+  int conv_f_t(RConv& c, int nimg, const TensorIn& in, float* out, const RBN& bn, int act,
+               hipStream_t st) {
+    ConvShape s = c.s;
+    s.N = nimg;
+    TensorOut o;
+    o.p0 = out;
+    o.bs0 = (long)s.Cout * s.Ho * s.Wo;
+    o.bias = bn.tt;
+    o.act = act;
+    hipEvent_t e = prof_begin(st);
+    MD2_TRY(conv_fwd(s, in, c.wpt, o, ws_conv(), st));
+    prof_end(e, c.cat, conv_flops(s), st, "fwd", &s);
+    return MD2_OK;
+  }
+  // The test-mode encoder: no statistics or apply pass.  The activations land in the buffers of
+  // the train-mode forward (md2_model_features / md2_model_debug_tensor read them as before;
+  // "....conv<k>.y" of a conv followed by a ReLU is not written).  The downsample branch runs on
+  // the model stream (three or four 1x1 convs per forward: the side-stream overlap is dropped
+  // here); the pose branch keeps its overlap (forward()).
+  int encoder_fwd_test(const TensorIn& in, int nimg, hipStream_t st) {
+    const long hw0 = (long)H0 * W0;
+    MD2_TRY(conv_f(stem, nimg, in, y0, 64 * hw0, ACT_NONE, 0, st));
+    {
+      hipEvent_t e = prof_begin(st);
+      MD2_TRY(affine_relu_maxpool(y0, stem_bn.ts, stem_bn.tt, nimg, 64, H0, W0, f0, mp, st));
+      prof_end(e, PROF_NCAT, 4.0 * nimg * 64 * (2.0 * hw0 + (double)Hm * Wm), st, "affine_relu_maxpool");
+    }
+    for (auto& sg : stages)
+      for (auto& b : sg) {
+        const float* x = b.in;
+        int C = b.Cin;
+        long HW = (long)b.Hin * b.Win;
+        for (size_t k = 0; k < b.st.size(); ++k) {
+          EncStage& e = b.st[k];
+          const bool last = k + 1 == b.st.size();
+          MD2_TRY(conv_f_t(e.conv, nimg, tin(x, C, HW), last ? e.y : e.a, e.bn, last ? ACT_NONE : ACT_RELU, st));
+          x = e.a;
+          C = e.conv.p.cout;
+          HW = (long)e.conv.s.Ho * e.conv.s.Wo;
+        }
+        EncStage& last = b.st.back();
+        const float* res = b.in;
+        if (b.down) {
+          side_ws = true;   // the downsample conv's split-K workspace is sized on the side set
+          const int rc = conv_f_t(b.dconv, nimg, tin(b.in, b.Cin, (long)b.Hin * b.Win), b.yd, b.dbn, ACT_NONE, st);
+          side_ws = false;
+          MD2_TRY(rc);
+          res = b.yd;
+        }
+        const long n = (long)nimg * b.C * b.H * b.W;
+        hipEvent_t e = prof_begin(st);
+        MD2_TRY(add_relu(last.y, res, last.a, n, st));
+        prof_end(e, PROF_NCAT, 12.0 * n, st, "add_relu");
+      }
+    return MD2_OK;
+  }
+  int encoder(const TensorIn& in, int nimg, hipStream_t st) {
+    return testmode ? encoder_fwd_test(in, nimg, st) : encoder_fwd(in, nimg, st);
+  }
+
   // ---- encoder forward over nimg images (input already mapped by `in`)
   int encoder_fwd(const TensorIn& in, int nimg, hipStream_t st) {
     const long hw0 = (long)H0 * W0;
@@ -1162,7 +1325,7 @@ class Model {
     in.bdiv = N;          // image b = l*N + n  ->  x[n][l]
     in.bs0 = 3 * fs;
     in.bhi = fs;
-    MD2_TRY(encoder_fwd(in, B, st));
+    MD2_TRY(encoder(in, B, st));
     if (pose_overlap()) {
       MD2_TRY(stream_wait(st, side, fork_ev));
       MD2_TRY(pose_fwd(side));
@@ -1679,9 +1842,19 @@ int model_create(const ModelCfg& cfg, float* params, float* grads, Model** out) 
 
 void model_destroy(Model* m) { delete m; }
 
+// every training entry point in test mode: the activations a backward needs are not kept and the
+// folded packs do not follow an update
+static int refuse_testmode(const Model* m, const char* what) {
+  if (!m->testmode) return MD2_OK;
+  set_error(std::string(what) + ": the model is in test mode (md2_model_set_testmode(m, 0, stream) "
+            "returns to training)");
+  return MD2_ESTATE;
+}
+
 int model_forward_loss(Model* m, const float* x, const float* automask, float* loss, float* terms,
                        hipStream_t st) {
   MD2_CHECK_ARG(m && x, "model/x");
+  MD2_TRY(refuse_testmode(m, "forward_loss"));
   MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
   m->cur_x = x;
   m->cot_ready = 1;
@@ -1691,13 +1864,15 @@ int model_forward_loss(Model* m, const float* x, const float* automask, float* l
 int model_forward(Model* m, const float* x, hipStream_t st) {
   MD2_CHECK_ARG(m && x, "model/x");
   MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
-  m->cur_x = x;
+  // test mode: forward only -- nothing a backward could start from is kept
+  m->cur_x = m->testmode ? nullptr : x;
   m->cot_ready = 0;
   return m->forward(x, st);
 }
 
 int model_set_cotangents(Model* m, const float* const* d_disp, const float* d_pose, hipStream_t st) {
   MD2_CHECK_ARG(m, "model");
+  MD2_TRY(refuse_testmode(m, "set_cotangents"));
   if (!m->cur_x) {
     set_error("set_cotangents: no pending forward (none yet, or eval_disparity ran since)");
     return MD2_ESTATE;
@@ -1766,6 +1941,7 @@ static int capture_step(Model* m, bool with_auto, float* adam_m, float* adam_v, 
 int model_train_step_graph(Model* m, const float* x, const float* auto_loss, float* adam_m,
                            float* adam_v, float lr, int step, float* loss, hipStream_t st) {
   MD2_CHECK_ARG(m && x && adam_m && adam_v && loss && step >= 1, "train_step_graph args");
+  MD2_TRY(refuse_testmode(m, "train_step_graph"));
   auto& g = m->g;
   const bool with_auto = auto_loss != nullptr;
   if (m->prof) {   // per-launch HIP events cannot live in a replayed graph: eager step
@@ -1796,6 +1972,7 @@ int model_train_step_graph(Model* m, const float* x, const float* auto_loss, flo
 
 int model_backward_segment(Model* m, int k, long* off, long* len, hipStream_t st) {
   MD2_CHECK_ARG(m, "model");
+  MD2_TRY(refuse_testmode(m, "backward_segment"));
   if (!m->cur_x) {
     set_error("backward_segment: no pending forward_loss (none yet, or eval_disparity ran since)");
     return MD2_ESTATE;
@@ -1823,6 +2000,7 @@ int model_backward_segment(Model* m, int k, long* off, long* len, hipStream_t st
 int model_adam(Model* m, float* adam_m, float* adam_v, float lr, float b1, float b2, float eps,
                int step, float grad_scale, hipStream_t st) {
   MD2_CHECK_ARG(m && adam_m && adam_v && step >= 1, "adam args");
+  MD2_TRY(refuse_testmode(m, "adam"));
   MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
   const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
   MD2_TRY(adam_step(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, b1, b2, eps, (float)bc1,
@@ -1834,6 +2012,7 @@ int model_adam_segment(Model* m, int k, float* adam_m, float* adam_v, float lr, 
                        float eps, int step, float grad_scale, hipStream_t st) {
   MD2_CHECK_ARG(m && adam_m && adam_v && step >= 1, "adam_segment args");
   MD2_CHECK_ARG(k >= 0 && k < 6, "segment index");
+  MD2_TRY(refuse_testmode(m, "adam_segment"));
   const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
   return m->adam_segment(k, adam_m, adam_v, lr, b1, b2, eps, (float)bc1, (float)bc2, grad_scale, st);
 }
@@ -1854,7 +2033,8 @@ bool model_segment_update_enabled() {
 int model_repack(Model* m, hipStream_t st) {
   MD2_CHECK_ARG(m, "model");
   MD2_TRY(m->adam_join(st));   // pending per-segment updates write the same packed weights
-  return m->repack(st);
+  MD2_TRY(m->repack(st));
+  return m->testmode ? m->refold(st) : MD2_OK;
 }
 
 int model_debug_tensor(Model* m, int index, const char** name, const void** ptr, int* dims) {
@@ -1955,7 +2135,7 @@ int model_eval_disparity(Model* m, const float* x, int n, float** disp_out, hipS
   // backward after this must fail instead of differentiating the eval batch
   m->cur_x = nullptr;
   TensorIn in = Model::tin(x, m->cfg.arch.in_ch, (long)m->cfg.H * m->cfg.W);
-  MD2_TRY(m->encoder_fwd(in, n, st));
+  MD2_TRY(m->encoder(in, n, st));
   MD2_TRY(m->decoder_fwd(n, 0, st));
   if (disp_out) {
     int li = 0;
@@ -2000,7 +2180,8 @@ int model_set_params_flux(Model* m, const float* flux, hipStream_t st) {
   MD2_CHECK_ARG(m, "model");
   MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
   MD2_TRY(flux_flip_copy(m, flux, m->params, st));
-  return m->repack(st);
+  MD2_TRY(m->repack(st));
+  return m->testmode ? m->refold(st) : MD2_OK;
 }
 
 int model_get_params_flux(Model* m, float* flux, hipStream_t st) {
@@ -2018,7 +2199,9 @@ int model_get_grads_flux(Model* m, float* flux, hipStream_t st) {
 // train_loss pullback with an upstream cotangent: the fused loss tail formed d loss / d (disp,
 // pose) for dloss = 1 during the forward; scale them before backward segment 0
 int model_scale_loss_cotangent(Model* m, float dloss, hipStream_t st) {
-  MD2_CHECK_ARG(m && m->cur_x && m->cot_ready, "loss cotangent before forward_loss");
+  MD2_CHECK_ARG(m, "model");
+  MD2_TRY(refuse_testmode(m, "loss_cotangent"));
+  MD2_CHECK_ARG(m->cur_x && m->cot_ready, "loss cotangent before forward_loss");
   if (dloss == 1.f) return MD2_OK;
   for (auto& d : m->br)
     if (d.head >= 0) MD2_TRY(scale_inplace(d.d_head, (long)m->ND * 4 * d.h * d.w, dloss, st));
@@ -2034,6 +2217,62 @@ int model_set_bins(Model* m, const float* bins, hipStream_t st) {
   MD2_HIP(hipMemcpyAsync(m->bins, bins, sizeof(float) * m->N * m->NP, hipMemcpyDefault, st));
   return MD2_OK;
 }
+
+// ---- BatchNorm running statistics as model state, test mode (testmode.h)
+int arch_bn_stat_count(const ArchCfg& a, long* n_bn, long* n_elems) {
+  long nb = 0, ne = 0;
+  for (const ParamEntry& e : build_param_table(a))
+    if (e.name.size() > 6 && e.name.compare(e.name.size() - 6, 6, ".gamma") == 0) {
+      ++nb;
+      ne += 2 * e.numel;
+    }
+  if (n_bn) *n_bn = nb;
+  if (n_elems) *n_elems = ne;
+  return MD2_OK;
+}
+
+int model_get_bn_stats(Model* m, float* out, hipStream_t st) {
+  MD2_CHECK_ARG(m && out, "get_bn_stats args");
+  MD2_TRY(m->adam_join(st));
+  MD2_HIP(hipMemcpyAsync(out, m->bn_stats, sizeof(float) * (size_t)m->bn_layout.off[m->bn_layout.n],
+                         hipMemcpyDeviceToDevice, st));
+  return MD2_OK;
+}
+
+int model_set_bn_stats(Model* m, const float* in, hipStream_t st) {
+  MD2_CHECK_ARG(m && in && in != m->bn_stats, "set_bn_stats args");
+  MD2_TRY(m->adam_join(st));
+  // checked on the device; only the 4-byte verdict crosses to the host
+  MD2_HIP(hipMemsetAsync(m->bn_flag, 0, sizeof(int), st));
+  MD2_TRY(bn_stats_validate(in, m->bn_layout, m->bn_flag, st));
+  int bad = 0;
+  MD2_HIP(hipMemcpyAsync(&bad, m->bn_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  MD2_HIP(hipStreamSynchronize(st));
+  MD2_CHECK_ARG(!bad, "set_bn_stats: a variance is negative or an entry is not finite (state unchanged)");
+  MD2_HIP(hipMemcpyAsync(m->bn_stats, in, sizeof(float) * (size_t)m->bn_layout.off[m->bn_layout.n],
+                         hipMemcpyDeviceToDevice, st));
+  return m->testmode ? m->refold(st) : MD2_OK;
+}
+
+int model_set_testmode(Model* m, int on, hipStream_t st) {
+  MD2_CHECK_ARG(m, "model");
+  if (!on) {
+    m->testmode = false;   // the train-mode packs and the running statistics were never touched
+    return MD2_OK;
+  }
+  if (m->E > 0) {
+    set_error("set_testmode: the MPI mode has no inference path (eval_disparity is unsupported there)");
+    return MD2_ENOTSUP;
+  }
+  MD2_TRY(m->adam_join(st));
+  MD2_TRY(m->testmode_alloc());
+  MD2_TRY(m->refold(st));
+  m->testmode = true;
+  m->cur_x = nullptr;      // a pending train forward is discarded, as by eval_disparity
+  return MD2_OK;
+}
+
+int model_testmode(Model* m) { return m && m->testmode ? 1 : 0; }
 
 long model_param_count(Model* m) { return m ? m->spec.total : 0; }
 float* model_grads(Model* m) { return m ? m->grads : nullptr; }

@@ -101,6 +101,16 @@ int model_get_params_flux(Model* m, float* flux, hipStream_t st);
 int model_get_grads_flux(Model* m, float* flux, hipStream_t st);
 // scale the loss-tail gradients of the last forward by the train_loss cotangent
 int model_scale_loss_cotangent(Model* m, float dloss, hipStream_t st);
+// BatchNorm running statistics as one flat vector: per BatchNorm (in the order of the gamma
+// entries of the parameter table) C means then C variances; device pointers.  set refuses a
+// negative / non-finite entry (MD2_EINVAL, state unchanged) and re-folds in test mode.
+int arch_bn_stat_count(const ArchCfg& a, long* n_bn, long* n_elems);
+int model_get_bn_stats(Model* m, float* out, hipStream_t st);
+int model_set_bn_stats(Model* m, const float* in, hipStream_t st);
+// test mode (Flux testmode!): forward / eval_disparity run BatchNorm on the running statistics,
+// folded into the convs; every training entry point returns MD2_ESTATE until it is switched off
+int model_set_testmode(Model* m, int on, hipStream_t st);
+int model_testmode(Model* m);
 float* model_grads(Model* m);          // the caller-owned flat gradient vector
 size_t model_device_bytes(Model* m);
 

@@ -144,6 +144,11 @@ _SIGS = {
     "md2_model_outputs": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_void_p)]),
     "md2_model_eval_disparity": (C.c_int, [P, P, C.c_int, C.POINTER(C.c_void_p), P]),
+    "md2_arch_bn_stat_count": (C.c_int, [C.POINTER(ModelCfg), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "md2_model_get_bn_stats": (C.c_int, [P, P, P]),
+    "md2_model_set_bn_stats": (C.c_int, [P, P, P]),
+    "md2_model_set_testmode": (C.c_int, [P, C.c_int, P]),
+    "md2_model_testmode": (C.c_int, [P]),
     "md2_model_debug_tensor": (C.c_int, [P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int)]),
     "md2_model_features": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),

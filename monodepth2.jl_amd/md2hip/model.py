@@ -160,14 +160,44 @@ class _Executor:
         self.forwarded = False              # a forward_loss ran since the last eval_disparity here
         self.pending = False                # ... and its backward has not run yet
         self.version = -1                   # Model.version its packed conv weights reflect
+        self.bn_version = 0                 # Model.bn_version its running statistics reflect (0: 0 / 1)
+        self.testmode = False
         self.sync()
 
     def sync(self):
-        """Re-pack this executor's conv weights if the flat parameters changed since its last
-        pack (ADAM through another executor, load_flat, direct writes via Model.touch())."""
-        if self.version != self.model.version:
-            check(lib().md2_model_repack(self.handle, stream_of(self.model.device)), "md2_model_repack")
-            self.version = self.model.version
+        """Bring this executor up to the model: re-pack its conv weights if the flat parameters
+        changed since its last pack (ADAM through another executor, load_flat, direct writes via
+        Model.touch()), install the model's BatchNorm running statistics if another executor moved
+        them or ``load_bn_stats`` replaced them, and switch its mode (``Model.testmode``).  The
+        switch to test mode comes last, so the library folds the statistics into the weights once."""
+        m = self.model
+        st = stream_of(m.device)
+        if self.testmode and not m._testmode:
+            check(lib().md2_model_set_testmode(self.handle, 0, st), "md2_model_set_testmode")
+            self.testmode = False
+        if self.version != m.version:
+            check(lib().md2_model_repack(self.handle, st), "md2_model_repack")
+            self.version = m.version
+        if m._bn_owner is not None and m._bn_owner is not self:
+            m._pull_bn_stats()
+        if self.bn_version != m.bn_version:
+            check(lib().md2_model_set_bn_stats(self.handle, ptr(m._bn_stats), st), "md2_model_set_bn_stats")
+            self.bn_version = m.bn_version
+        if m._testmode and not self.testmode:
+            check(lib().md2_model_set_testmode(self.handle, 1, st), "md2_model_set_testmode")
+            self.testmode = True
+
+    def get_bn_stats(self):
+        """This executor's running statistics (md2_model_get_bn_stats), a fresh flat tensor."""
+        import torch
+        out = torch.empty(self.model.bn_numel, dtype=torch.float32, device=self.model.device)
+        check(lib().md2_model_get_bn_stats(self.handle, ptr(out), stream_of(self.model.device)),
+              "md2_model_get_bn_stats")
+        return out
+
+    def _trained(self):
+        """A train-mode forward ran here: this executor now holds the newest running statistics."""
+        self.model._bn_owner = self
 
     def __del__(self):
         try:
@@ -219,27 +249,33 @@ class _Executor:
 
     def forward_loss(self, x, auto_loss=None, loss=None, terms=None):
         import torch
+        self.model._require_train("train_loss / forward_loss")
         loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=x.device)
         self.sync()
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
         check(lib().md2_model_forward_loss(self.handle, ptr(x), ptr(am), ptr(loss), ptr(terms),
                                            stream_of(x.device)), "md2_model_forward_loss")
         self.forwarded = self.pending = True
+        self._trained()
         return loss
 
     def forward(self, x):
         """``(m)(x, source_ids, target_id)`` alone (md2_model_forward): encoder, DepthDecoder and
-        PoseDecoder, no loss tail.  A backward after it needs ``set_cotangents``."""
+        PoseDecoder, no loss tail.  A backward after it needs ``set_cotangents``.  In test mode
+        (``Model.testmode``) BatchNorm runs on the running statistics and no backward can follow."""
         self.sync()
         check(lib().md2_model_forward(self.handle, ptr(x), None, None, stream_of(x.device)),
               "md2_model_forward")
-        self.forwarded = self.pending = True
+        self.forwarded = self.pending = not self.testmode
         self.cotangents = False
+        if not self.testmode:
+            self._trained()
 
     def set_cotangents(self, d_disps=None, d_pose=None):
         """The cotangents of the last forward's outputs (md2_model_set_cotangents): d_disps[l] like
         the level-l disparities (None: zero), d_pose like the [2N, 6] poses (None: zero)."""
         import torch
+        self.model._require_train("pullback / set_cotangents")
         keep = []
         arr = (C.c_void_p * 5)()
         for i, d in enumerate(d_disps or []):
@@ -258,6 +294,7 @@ class _Executor:
         captured hipGraph (md2_model_train_step_graph): the same kernels in the same order as
         forward_loss + backward + ADAM.update, without per-launch host work.  Returns the loss."""
         import torch
+        self.model._require_train("train_step_graph")
         if tuple(opt.beta) != (0.9, 0.999) or opt.eps != 1e-8:
             raise NotImplementedError("the captured step uses ADAM's defaults beta=(0.9, 0.999), eps=1e-8")
         loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=x.device)
@@ -271,12 +308,14 @@ class _Executor:
                                                opt.t, ptr(loss), stream_of(x.device)),
               "md2_model_train_step_graph")
         self.forwarded = True
+        self._trained()
         self.model._last = self
         self.model.touch()
         self.version = self.model.version
         return loss
 
     def backward_segment(self, k):
+        self.model._require_train("gradient / backward")
         off, ln = C.c_longlong(), C.c_longlong()
         check(lib().md2_model_backward_segment(self.handle, k, C.byref(off), C.byref(ln),
                                                stream_of(self.model.device)), "md2_model_backward_segment")
@@ -351,6 +390,63 @@ class Model:
         # bumped whenever the flat parameters change; every executor keeps its own packed copy of
         # the conv weights and re-packs lazily when it is behind (Model.executor / _Executor.sync)
         self.version = 0
+        # BatchNorm running statistics (Flux BatchNorm's mu / sigma^2): one flat vector, per
+        # BatchNorm in the order of its gamma entry C means then C variances (md2_model_get_bn_stats).
+        # They follow the parameters, not the shape: the executor that ran the newest train-mode
+        # forward owns the truth (_bn_owner); any other executor receives it before its next use
+        # (_Executor.sync, bn_version as `version` for the weights).
+        self.bn_channels = [int(np.prod(shape)) for name, shape, _ in self.table if name.endswith(".gamma")]
+        self.bn_numel = 2 * sum(self.bn_channels)
+        self._bn_stats = torch.cat([torch.cat([torch.zeros(c), torch.ones(c)]) for c in self.bn_channels]
+                                   ).to(self.device, torch.float32)
+        self.bn_version = 0
+        self._bn_owner: Optional[_Executor] = None
+        self._testmode = False
+
+    # -- BatchNorm running statistics, test mode (Flux testmode!) ----------------------------
+    def _pull_bn_stats(self):
+        ex, self._bn_owner = self._bn_owner, None
+        if ex is not None:
+            self._bn_stats = ex.get_bn_stats()
+            self.bn_version += 1
+            ex.bn_version = self.bn_version
+
+    def bn_stats(self):
+        """The running statistics as one flat fp32 tensor (a copy): those of the executor that ran
+        the most recent train-mode forward, else the loaded / initial (0, 1) state."""
+        self._pull_bn_stats()
+        return self._bn_stats.clone()
+
+    def load_bn_stats(self, t):
+        """Install running statistics (``bn_stats`` layout); every executor receives them before
+        its next use.  ValueError for a wrong length, a negative variance or a non-finite entry."""
+        import torch
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() != self.bn_numel:
+            raise ValueError(f"bn_stats has {t.numel()} elements, the model's BatchNorms need {self.bn_numel}")
+        t = t.to(self.device, torch.float32).clone()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("bn_stats: non-finite entry")
+        off = 0
+        for c in self.bn_channels:
+            if bool((t[off + c:off + 2 * c] < 0).any()):
+                raise ValueError("bn_stats: negative variance")
+            off += 2 * c
+        self._bn_stats = t
+        self._bn_owner = None
+        self.bn_version += 1
+
+    def testmode(self, on: bool = True):
+        """Flux ``testmode!(model, on)``: while on, ``eval_disparity`` and ``model(x, ...)`` normalise
+        with the running statistics (folded into the convs; a sample's result no longer depends on
+        its batch, and the statistics are not modified), and every training call raises.
+        ``testmode(False)`` returns to training with the train-mode state untouched."""
+        self._testmode = bool(on)
+        return self
+
+    def _require_train(self, what):
+        if self._testmode:
+            raise RuntimeError(f"{what}: the model is in test mode -- call model.testmode(False) to train")
 
     # -- parameters (Flux.params(model)) ----------------------------------------------------
     def parameters(self) -> Dict[str, object]:
@@ -368,6 +464,8 @@ class Model:
         """Free the cached executors (all, or those of one batch size)."""
         for k in [k for k in self._ex if batch is None or k[0] == batch]:
             ex = self._ex.pop(k)
+            if ex is self._bn_owner:
+                self._pull_bn_stats()       # its running statistics stay with the model
             if ex is self._last:
                 self._last = None
 
@@ -445,6 +543,7 @@ def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
     the backward.  Returns (loss, vis_disparity, vis_warped, vis_loss).  MPI mode (the model's
     DepthDecoder has embedding_levels > 0; batch 1): ``num_bins`` planes, ``bins`` [1, num_bins]
     (default: a fresh draw of md2hip.disparity_bins)."""
+    model._require_train("train_loss")
     ex = model.executor(tuple(x.shape), cache, params, num_bins)
     if ex.emb:
         ex.set_bins(disparity_bins(x.shape[0], num_bins, device=x.device) if bins is None else bins)
@@ -475,6 +574,7 @@ def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
 def gradient(model: Model, dloss: float = 1.0):
     """Backward of the last ``train_loss`` (Zygote ``gradient(θ)``): fills ``model.grad``.
     ``dloss`` is the upstream cotangent of the loss (the ``rrule`` pullback's input)."""
+    model._require_train("gradient")
     ex = model._last
     if not ex.forwarded:
         raise RuntimeError("gradient() needs a preceding train_loss()")
@@ -492,6 +592,7 @@ def pullback(model: Model, d_disps=None, d_poses=None):
     (None: zero); ``d_poses`` [Pose-like (d_rvec [N, 3], d_tvec [N, 3]) per source] or a [2N, 6]
     tensor (None: zero).  The backward segments are the fused path's (md2_model_set_cotangents)."""
     import torch
+    model._require_train("pullback")
     ex = model._last
     if ex is None or not ex.forwarded:
         raise RuntimeError("pullback() needs a preceding model(x, source_ids, target_id) call")
@@ -539,6 +640,7 @@ class ADAM:
     def update(self, model: Model, grad_scale: float = 1.0):
         """``Flux.Optimise.update!(opt, θ, ∇)`` on the flat vector (in place)."""
         import torch
+        model._require_train("ADAM.update")
         if self.m is None:
             self.m = torch.zeros_like(model.flat)
             self.v = torch.zeros_like(model.flat)
@@ -557,6 +659,7 @@ class ADAM:
         """The update of backward segment k's parameters alone (md2_model_adam_segment), beside the
         rest of the backward; segment 0 opens the step.  ``finish`` closes it."""
         import torch
+        model._require_train("ADAM.update_segment")
         if self.m is None:
             self.m = torch.zeros_like(model.flat)
             self.v = torch.zeros_like(model.flat)
@@ -580,6 +683,7 @@ class ADAM:
 
 def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, opt: ADAM):
     """One ``gradient(θ) do train_loss(...)[1] end`` + ``update!`` on one GPU."""
+    model._require_train("train_step")
     loss, *_ = train_loss(model, x, auto_loss, cache, params)
     gradient(model)
     opt.update(model)
@@ -587,8 +691,9 @@ def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, op
 
 
 def eval_disparity(model: Model, x, cache: Optional[TrainCache] = None):
-    """``eval_disparity(m, x)`` (src/model.jl:63) for x [N, C, H, W] (train-mode BatchNorm, as
-    the reference never calls testmode!).  Runs on any cached executor of batch >= N at (H, W)
+    """``eval_disparity(m, x)`` (src/model.jl:63) for x [N, C, H, W]: train-mode BatchNorm by
+    default (the reference never calls testmode!; the running statistics move as a side effect),
+    the running statistics after ``model.testmode()``.  Runs on any cached executor of batch >= N at (H, W)
     (``Model.eval_executor``; its weights are re-packed first if stale); ``cache`` is unused
     (inference has no loss) and kept for signature compatibility."""
     N, Cc, H, W = x.shape
@@ -602,6 +707,8 @@ def eval_disparity(model: Model, x, cache: Optional[TrainCache] = None):
     ex.forwarded = False            # the library discards any pending forward of this executor
     check(lib().md2_model_eval_disparity(ex.handle, ptr(x), N, dptr, stream_of(x.device)),
           "md2_model_eval_disparity")
+    if not ex.testmode:
+        ex._trained()
     out = []
     h, w = H, W
     nl = len(model.depth_decoder.scale_levels)
