@@ -1,3 +1,57 @@
-// Implicit-GEMM conv: forward pass launchers (see conv_impl.inc).
-#define MD2_CONV_PART 1
-#include "conv_impl.inc"
+// Implicit-GEMM conv: the forward pass (kernels and launchers: conv_px_launch.h).
+#include "conv_px_launch.h"
+
+namespace md2 {
+
+int conv_fwd(const ConvShape& s, const TensorIn& x, const float* wpacked, const TensorOut& y,
+             ConvWorkspace ws, hipStream_t st, SplitKDefer* defer) {
+  if (defer) {
+    const SplitKDefer req = *defer;   // kept: launch_px reads the request
+    *defer = SplitKDefer{};
+    defer->stats = req.stats;
+    defer->keep_reduce = req.keep_reduce;
+  }
+  MD2_TRY(check_shape(s));
+  MD2_CHECK_ARG(x.p0 && wpacked && y.p0, "conv_fwd pointers");
+  MD2_CHECK_ARG(x.c0 == s.Cin || x.p1 != nullptr, "conv_fwd: second input tensor missing");
+  MD2_CHECK_ARG(x.c0 >= s.Cin || !conv_tap_major(s, 0) || x.c0 % 16 == 0,
+                "conv_fwd: concat split must be a multiple of 16 channels");
+  if (head_path(s) && x.c0 >= s.Cin && y.c0 >= 1) {
+    MD2_CHECK_ARG(!conv_px2_used(s, 0), "head: packed layout");
+    conv_arith_ref() = 0;
+    return head_fwd(s, conv_head_in(x), conv_head_w(s, 0, wpacked), y.bias, y.act, y.p0, y.bs0,
+                    y.accumulate, st);
+  }
+  ConvArgs a{};
+  fill_common(a, s);
+  a.g.M = s.Cout;
+  a.g.N = (long)s.N * s.Ho * s.Wo;
+  a.g.K = s.Cin * s.KH * s.KW;
+  a.g.Mpad = (int)round_up(s.Cout, MPAD);
+  a.fd_pix = make_fastdiv((uint32_t)(s.Ho * s.Wo));
+  a.fd_row = make_fastdiv((uint32_t)s.Wo);
+  a.fd_bdiv = make_fastdiv((uint32_t)std::min(x.bdiv, 1 << 30));
+  a.in = x;
+  a.A = wpacked;
+  a.out = y;
+  a.A_bytes = (uint32_t)(conv_fwd_packed_elems(s) * sizeof(float));
+  {
+    long ext0 = 0;
+    for (int b = 0; b < s.N; ++b)
+      ext0 = std::max(ext0, (long)(b % x.bdiv) * x.bs0 + (long)(b / x.bdiv) * x.bhi);
+    ext0 += (long)x.c0 * s.H * s.W;
+    const long ext1 = x.p1 ? (long)(s.N - 1) * x.bs1 + (long)(s.Cin - x.c0) * s.H * s.W : 0;
+    MD2_CHECK_ARG(ext0 * 4 < (long)OOB && ext1 * 4 < (long)OOB, "conv_fwd: tensor exceeds 2 GB");
+    a.b0_bytes = (uint32_t)(ext0 * 4);
+    a.b1_bytes = (uint32_t)(ext1 * 4);
+  }
+  if (stem_s2d_applies(s, x, y)) {   // (statistics: the separate pass)
+    conv_arith_ref() = 6;
+    return stem_s2d_launch(s, a, st);
+  }
+  const bool bk32 = conv_tap_major(s, 0) && s.Cin % 32 == 0 && (x.c0 >= s.Cin || x.c0 % 32 == 0);
+  const Plan p = plan_px(a.g.M, a.g.N, a.g.K, bk32);
+  return launch_px<0>(s, a, p, ws, st, defer);
+}
+
+}  // namespace md2

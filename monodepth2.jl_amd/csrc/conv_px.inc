@@ -1,5 +1,5 @@
 // ---------------------------------------------------------------------------------------------
-// forward / dgrad implicit-GEMM kernel (B operand lanes along pixels); included by conv.hip.
+// forward / dgrad implicit-GEMM kernel (B operand lanes along pixels); included by conv_px_launch.h.
 // MODE 0 = forward (im2col of x), MODE 1 = dgrad (gather of dY).
 //
 // Operands come in through raw buffer loads with 32-bit byte offsets; a tap outside the image

@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------
 // forward / dgrad implicit-GEMM kernel for M <= 16 (the 16-channel full-resolution DepthDecoder
-// convs: Cout = 16 forward, Cin = 16 data gradient); included by conv_impl.inc after
+// convs: Cout = 16 forward, Cin = 16 data gradient); included by conv_px_launch.h after
 // conv_px2.inc.  MODE 0 = forward, MODE 1 = dgrad; tap-major K only (C % 16 == 0), no split-K.
 //
 // A 32-row MFMA tile would leave half its rows idle here, so the contraction runs on
@@ -14,8 +14,6 @@
 // (px2_gather: wave w loads channels 4w..4w+3 of the chunk, wave-uniform scalar soffsets).
 // Output layout of the 16x16x4 MFMA: lane l holds column j = l & 15, rows 4*(l >> 4) + r.
 // ---------------------------------------------------------------------------------------------
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int MODE, int BN, int KH, int KW, int S, int RFL>
 __global__ __launch_bounds__(256) void conv_px16_kernel(ConvArgs a) {

@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------
 // forward / dgrad implicit-GEMM kernel, k-contiguous LDS images (tap-major K only); included by
-// conv.hip after conv_px.inc.  MODE 0 = forward, MODE 1 = dgrad.
+// conv_px_launch.h after conv_px.inc.  MODE 0 = forward, MODE 1 = dgrad.
 //
 // Per 16-deep K chunk the LDS holds As[m][k] and Bs[n][k] with k contiguous (rows of 20 floats:
 // the 80-byte stride keeps each 8-lane ds_read_b128 phase on distinct 16-byte bank groups).  The

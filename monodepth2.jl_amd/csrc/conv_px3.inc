@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------
 // forward / dgrad implicit-GEMM kernel on the bf16 MFMA with EXACT fp32 products (bf16x9);
-// included by conv_impl.inc after conv_px2.inc.  MODE 0 = forward, MODE 1 = dgrad; tap-major K.
+// included by conv_px_launch.h after conv_px2.inc.  MODE 0 = forward, MODE 1 = dgrad; tap-major K.
 //
 // Every fp32 operand x is split exactly into three bf16 terms, x = hi + mid + lo: hi = x rounded
 // to bf16, mid = the exact remainder x - hi rounded to bf16, lo = the rest (<= 8 significant
@@ -22,37 +22,6 @@
 //      packed LDS format), and stored as three k-contiguous bf16 images Bs[part][n][k] (48-byte
 //      rows: the 16-lane phases of a ds_read_b128 hit distinct banks).
 // ---------------------------------------------------------------------------------------------
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
-// exact three-way split of two fp32 values into packed bf16 pairs (hi, mid, lo): each remainder
-// of a round-to-nearest bf16 is exact in fp32, and the second remainder has <= 8 significant bits
-__device__ __forceinline__ void split3_pk(float a, float b, uint32_t& h, uint32_t& m, uint32_t& l) {
-  const f32x2_t x = {a, b};
-  const bf16x2_t hb = __builtin_convertvector(x, bf16x2_t);
-  const f32x2_t r1 = x - __builtin_convertvector(hb, f32x2_t);
-  const bf16x2_t mb = __builtin_convertvector(r1, bf16x2_t);
-  const f32x2_t r2 = r1 - __builtin_convertvector(mb, f32x2_t);
-  h = __builtin_bit_cast(uint32_t, hb);
-  m = __builtin_bit_cast(uint32_t, mb);
-  l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r2, bf16x2_t));
-}
-
-__device__ __forceinline__ u32x4_t bload16(__amdgpu_buffer_rsrc_t r, uint32_t off_bytes) {
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off_bytes, 0, 0);
-  u32x4_t o;
-  o[0] = v[0];
-  o[1] = v[1];
-  o[2] = v[2];
-  o[3] = v[3];
-  return o;
-}
-
-// two bf16 (high halves of a, b) -> one dword, a in the low half
-__device__ __forceinline__ uint32_t pk_bf16(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xffff0000u); }
 
 // BK = 16 or 32: K depth per chunk (32: two 16-deep halves per barrier, the gather address maths
 // shared by 8 channels of one tap; needs the reduction channels % 32 == 0)

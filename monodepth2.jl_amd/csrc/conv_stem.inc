@@ -507,9 +507,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_stem_s2d_kernel(ConvArgs a,
   }
 }
 
-#if MD2_CONV_PART == 5
 bool stem_s2d_applies(const ConvShape& s, const TensorIn& x, const TensorOut& y) {
-  static const int on = env_int("MD2_STEM_S2D", 1);
+  static const int on = tuning_knob("MD2_STEM_S2D", 1);
   if (!on || s.KH != 7 || s.KW != 7 || s.stride != 2 || s.pad != 3 || s.reflect || s.Cin != 3 || s.Cout != 64) return false;
   if (s.cin_w && s.cin_w != 3) return false;
   if (s.H % 2 || s.W % 2 || s.Wo % 16 || s.Ho != s.H / 2 || s.Wo != s.W / 2) return false;
@@ -522,11 +521,10 @@ bool stem_s2d_applies(const ConvShape& s, const TensorIn& x, const TensorOut& y)
 // blocks: one per CU (256), at most one per output row
 static int stem_blocks(const ConvShape& s) { return (int)std::min<long>(256, (long)s.N * s.Ho); }
 
-
 // the filter-gradient kernel: the forward's conditions on the input and its own ring
 // (StemWgradLds: the pitch P, the combine buffer over the ring)
 bool stem_wgrad_s2d_applies(const ConvShape& s, const TensorIn& x) {
-  static const int on = env_int("MD2_WSTEM_S2D", 1);
+  static const int on = tuning_knob("MD2_WSTEM_S2D", 1);
   TensorOut y;
   if (!on || !stem_s2d_applies(s, x, y)) return false;
   return StemWgradLds::fits(s.Wo) && (long)s.N * s.Cout * s.Ho * s.Wo * 4 < (long)OOB;
@@ -568,4 +566,3 @@ int stem_s2d_launch(const ConvShape& s, const ConvArgs& a, hipStream_t st) {
 #endif
   return lds_launch<conv_stem_s2d_kernel<0>>(grid, block, z, st, a);
 }
-#endif

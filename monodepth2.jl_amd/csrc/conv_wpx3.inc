@@ -1,6 +1,6 @@
 // ---------------------------------------------------------------------------------------------
 // tap-major weight gradient on the bf16 MFMA with split products (the arithmetic of conv_px3);
-// included by conv_impl.inc after conv_px3.inc.
+// included by conv_wgrad.hip (split3_pk and the bf16 vector types: conv_kernel.h).
 //
 //   dW[m][tap*Cin + c] = sum_p dY[m][p] X[c][gather(p, tap)]     (K = the N*Ho*Wo pixels)
 //

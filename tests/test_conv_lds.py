@@ -34,14 +34,19 @@ def test_conv_lds_geometry_sweep(tmp_path):
 
 def test_lds_sizes_stated_only_in_the_header():
     """Planners and launchers keep no LDS byte count or plane formula of their own."""
-    for name in ("conv_impl.inc", "conv_halo.inc", "conv_stem.inc"):
+    names = sorted(n for n in os.listdir(CSRC) if n.startswith("conv") and n != "conv_lds.h")
+    assert names
+    attr_files = []
+    for name in names:
         src = open(os.path.join(CSRC, name)).read()
         for pat in (r"65536", r"163840", r"\b448\b", r"16 \* 7 \* 4", r"HX_PLANE =", r"\* 64\) \+ ",
                     r"hipFuncAttributeMaxDynamicSharedMemorySize"):
             hits = [m.start() for m in re.finditer(pat, src)]
-            # the one attribute call is lds_launch's (conv_impl.inc)
-            allowed = 1 if (pat.startswith("hipFunc") and name == "conv_impl.inc") else 0
+            # the one attribute call is lds_launch's, in the file that defines it
+            allowed = 1 if (pat.startswith("hipFunc") and re.search(r"\bint lds_launch\(", src)) else 0
             assert len(hits) == allowed, (name, pat, len(hits))
+            attr_files += [name] * (len(hits) if pat.startswith("hipFunc") else 0)
+    assert len(attr_files) == 1, attr_files
 
 
 def test_timing_variants_not_in_the_library():
