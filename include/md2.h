@@ -499,6 +499,57 @@ int md2_model_set_bn_stats(md2_model* m, const float* in, void* stream);
 int md2_model_set_testmode(md2_model* m, int on, void* stream);
 int md2_model_testmode(md2_model* m);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth evaluation: the Monodepth2 / Eigen protocol (median scaling, crop, seven error metrics)
+ * of a batch of predicted disparities against ground-truth depth, entirely on the device.
+ * Additive: MD2_ABI_VERSION is unchanged.
+ *
+ * For each image i of the n: disp[i] is [h][w] fp32, the network's sigmoid disparity (any level);
+ * gt[i] is [gt_h][gt_w] fp32 ground-truth depth, where 0 (or anything outside the evaluation
+ * range) means "no measurement".  All images of one call share gt_h x gt_w.
+ *  1. Scaled disparity  sd = disp * (1/min_depth - 1/max_depth) + 1/max_depth  (the inner term of
+ *     disparity_to_depth, src/utils.jl:179-183).
+ *  2. sd is resized to gt_h x gt_w by half-pixel-centre bilinear interpolation: at gt pixel (Y, X)
+ *     sx = clamp((X + 0.5) * w / gt_w - 0.5, 0, w - 1), sy alike (coordinates in fp64); the
+ *     neighbours are floor(sx) and min(floor(sx) + 1, w - 1).  When h == gt_h and w == gt_w the
+ *     sample is the input value itself.  pred = 1 / sd_resized.
+ *  3. Mask: eval_min < gt < eval_max (strict; false for NaN) and y0 <= Y < y1, x0 <= X < x1.
+ *     A masked pixel whose pred is not finite or not > 0 is a BAD pixel: counted in n_bad and
+ *     excluded from everything below.  count = the remaining pixels.
+ *  4. ratio = median(gt[mask]) / median(pred[mask]) with median_scaling, else cfg.scale.  The
+ *     median is exact (as NumPy's): the middle element for an odd count, 0.5f * (lo + hi) of the
+ *     two middle elements, in fp32, for an even count.  med_gt and med_pred are reported either way.
+ *  5. p = clamp(pred * ratio, eval_min, eval_max).
+ *  6. Over the mask, with g = gt:  abs_rel = mean(|g - p| / g),  sq_rel = mean((g - p)^2 / g),
+ *     rmse = sqrt(mean((g - p)^2)),  rmse_log = sqrt(mean((ln g - ln p)^2)),
+ *     a_k = mean(max(g / p, p / g) < 1.25^k), k = 1, 2, 3.
+ *  7. count == 0: the ten metrics are NaN and count = 0 (no fault).
+ * Per-pixel arithmetic and partial sums are fp32; block partials are combined in fp64.  Results are
+ * BITWISE REPRODUCIBLE from call to call: fixed grid, fixed-order reductions, integer atomics only.
+ * The call enqueues on `stream` and never synchronises with the host; it clears what it needs of
+ * the workspace itself (md2_depth_eval_workspace_size(cfg) bytes of device memory, any content).
+ * MD2_EINVAL (checked before any HIP call): a null pointer, n outside 1..65535, a size < 1,
+ * gt_h * gt_w > 2^24 (h * w > 2^30), a crop that is empty or outside the ground truth,
+ * min_depth >= max_depth, eval_min >= eval_max, a non-positive or non-finite bound, or
+ * median_scaling == 0 with a scale that is not positive and finite.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct md2_depth_eval_cfg {
+  int n, h, w;            /* disparity batch and size                     */
+  int gt_h, gt_w;         /* ground-truth size                            */
+  int y0, y1, x0, x1;     /* crop rectangle in gt pixels, half-open       */
+  float min_depth, max_depth;   /* disparity_to_depth range (0.1, 100)   */
+  float eval_min, eval_max;     /* valid gt range, clamp range (1e-3, 80) */
+  int median_scaling;     /* 1: per-image median ratio; 0: use scale      */
+  float scale;
+} md2_depth_eval_cfg;
+
+#define MD2_DEPTH_EVAL_NMETRIC 10
+/* metrics[i] = {abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio, med_gt, med_pred}
+   counts[i]  = {count, n_bad} */
+size_t md2_depth_eval_workspace_size(const md2_depth_eval_cfg* cfg);   /* 0 for an invalid cfg */
+int md2_depth_eval(const md2_depth_eval_cfg* cfg, const float* disp, const float* gt,
+                   float* metrics, int* counts, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

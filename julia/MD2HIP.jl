@@ -89,6 +89,16 @@ struct ConvDesc                                        # md2_conv_desc
     stride::Cint; pad::Cint; reflect::Cint; act::Cint
 end
 
+struct DepthEvalCfg                                    # md2_depth_eval_cfg
+    n::Cint; h::Cint; w::Cint
+    gt_h::Cint; gt_w::Cint
+    y0::Cint; y1::Cint; x0::Cint; x1::Cint
+    min_depth::Cfloat; max_depth::Cfloat
+    eval_min::Cfloat; eval_max::Cfloat
+    median_scaling::Cint
+    scale::Cfloat
+end
+
 # ------------------------------------------------------------------------------------------------
 # The model: Model(ResidualNetwork, DepthDecoder, PoseDecoder) with its parameters in ONE flat
 # device vector (Flux `params(model)` order, md2_arch_param_info) -- src/model.jl:24-70
@@ -672,6 +682,31 @@ function static_scores(x::ROCArray{Float32,5}; target_id=2, source_ids=(1, 3))
                 (Ptr{Float32}, Cint, Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{UInt8}, Ptr{Cvoid}),
                 x, n, C, H, W, target_id - 1, source_ids[1] - 1, source_ids[2] - 1, scores, ws, stream_ptr()))
     return Array(scores)
+end
+
+# Depth evaluation (Monodepth2 / Eigen protocol; include/md2.h states every step): disparities
+# disp (w,h,n) or (w,h,1,n) against ground-truth depth gt (Wg,Hg,n), one batched call, no host
+# sync.  crop: :garg, nothing (whole image) or 0-based half-open (y0, y1, x0, x1) in gt pixels.
+# Returns device arrays metrics (10, n) = abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, ratio,
+# med_gt, med_pred per image, and counts (2, n) = count, n_bad.  Data only: no rrule.
+garg_crop(gt_h, gt_w) = (floor(Int, 0.40810811 * gt_h), floor(Int, 0.99189189 * gt_h),
+                         floor(Int, 0.03594771 * gt_w), floor(Int, 0.96405229 * gt_w))
+function depth_errors(disp::ROCArray{Float32}, gt::ROCArray{Float32,3}; crop=:garg, min_depth=0.1f0,
+                      max_depth=100f0, eval_min=1f-3, eval_max=80f0, median_scaling=true, scale=1f0)
+    (ndims(disp) == 3 || (ndims(disp) == 4 && size(disp, 3) == 1)) || error("disp must be (w,h,n) or (w,h,1,n)")
+    w, h = size(disp, 1), size(disp, 2); n = size(disp, ndims(disp))
+    Wg, Hg = size(gt, 1), size(gt, 2)
+    n == size(gt, 3) || error("batch mismatch: disp has ", n, " images, gt ", size(gt, 3))
+    y0, y1, x0, x1 = crop === :garg ? garg_crop(Hg, Wg) : crop === nothing ? (0, Hg, 0, Wg) : crop
+    cfg = DepthEvalCfg(n, h, w, Hg, Wg, y0, y1, x0, x1, min_depth, max_depth, eval_min, eval_max,
+                       median_scaling ? 1 : 0, scale)
+    nbytes = ccall((:md2_depth_eval_workspace_size, lib), Csize_t, (Ref{DepthEvalCfg},), cfg)
+    ws = ROCVector{UInt8}(undef, max(nbytes, 256))      # an invalid cfg has size 0: the call says why
+    metrics = ROCArray{Float32}(undef, 10, n); counts = ROCArray{Int32}(undef, 2, n)
+    check(ccall((:md2_depth_eval, lib), Cint,
+                (Ref{DepthEvalCfg}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Cvoid}),
+                cfg, disp, gt, metrics, counts, ws, stream_ptr()))
+    return metrics, counts
 end
 
 function find_static(dataset, α; batch=16)

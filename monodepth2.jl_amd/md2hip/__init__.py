@@ -13,6 +13,7 @@ from .slow_depth import SlowDepth, adam_update, slow_depth  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .data import DataLoader, DChain, Depth10k, FlipX, KittyDataset, find_static  # noqa: F401
 from .mpi import MPIDepthDecoder, mpi_forward  # noqa: F401
+from .evaluate import METRIC_NAMES, depth_errors, evaluate_depth, garg_crop  # noqa: F401
 
 __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_poses", "lib", "MD2Error",
            "ADAM", "DepthDecoder", "Model", "Pose", "PoseDecoder", "ResidualNetwork", "ResNet",
@@ -20,4 +21,5 @@ __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_pos
            "train_step",
            "SlowDepth", "adam_update", "slow_depth", "load_checkpoint", "save_checkpoint",
            "DataLoader", "DChain", "Depth10k", "FlipX", "KittyDataset", "find_static",
-           "MPIDepthDecoder", "mpi_forward"]
+           "MPIDepthDecoder", "mpi_forward",
+           "METRIC_NAMES", "depth_errors", "evaluate_depth", "garg_crop"]

@@ -72,6 +72,17 @@ class WarpCfg(C.Structure):
     ]
 
 
+class DepthEvalCfg(C.Structure):
+    """``md2_depth_eval_cfg``."""
+    _fields_ = [
+        ("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("gt_h", C.c_int), ("gt_w", C.c_int),
+        ("y0", C.c_int), ("y1", C.c_int), ("x0", C.c_int), ("x1", C.c_int),
+        ("min_depth", C.c_float), ("max_depth", C.c_float),
+        ("eval_min", C.c_float), ("eval_max", C.c_float),
+        ("median_scaling", C.c_int), ("scale", C.c_float),
+    ]
+
+
 _lib = None
 _load_error = None
 
@@ -149,6 +160,8 @@ _SIGS = {
     "md2_model_set_bn_stats": (C.c_int, [P, P, P]),
     "md2_model_set_testmode": (C.c_int, [P, C.c_int, P]),
     "md2_model_testmode": (C.c_int, [P]),
+    "md2_depth_eval_workspace_size": (C.c_size_t, [C.POINTER(DepthEvalCfg)]),
+    "md2_depth_eval": (C.c_int, [C.POINTER(DepthEvalCfg), P, P, P, P, P, P]),
     "md2_model_debug_tensor": (C.c_int, [P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int)]),
     "md2_model_features": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
