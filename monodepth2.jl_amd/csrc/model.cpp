@@ -871,6 +871,12 @@ class Model {
     const char* v = getenv("MD2_FUSE_BNSTATS");
     return !(v && v[0] == '0');
   }();
+  // MD2_FUSE_BN_BWD=0 restores the two-pass BN backward (partials + apply) where a channel fits in
+  // one block of bn_bwd_channel (A/B, closeness test: the fp64 sums run in another order)
+  const bool fuse_bn_bwd = [] {
+    const char* v = getenv("MD2_FUSE_BN_BWD");
+    return !(v && v[0] == '0');
+  }();
   // MD2_FUSE_SPLITK=0 restores the separate reduction launches (A/B measurement)
   const bool fuse_splitk = [] {
     const char* v = getenv("MD2_FUSE_SPLITK");
@@ -1479,6 +1485,14 @@ class Model {
       prof_end(e, c.cat, conv_flops(s), st, "dgrad", &s);
       return bn_bwd(bn, da, nullptr, y, nimg, HW, dyprev, nullptr, 0, st, true);
     }
+    if (fuse_bn_bwd && bn_bwd_channel_fits(nimg, HW)) {
+      // the slabs are summed in the block's registers: DA (read by this backward alone) is not written
+      MD2_TRY(bn_bwd_channel(nullptr, SlabIn{d.slab, d.splits}, nullptr, y, bn.mean, bn.invstd,
+                             P(bn.p.g), P(bn.p.b), Gd(bn.p.g), Gd(bn.p.b), nimg, bn.p.c, HW, dyprev,
+                             nullptr, 0, st));
+      prof_end(e, c.cat, conv_flops(s), st, "dgrad", &s);
+      return MD2_OK;
+    }
     BNStatsWs w = bnws;
     w.parts = bn_parts(bn.p.c, nimg, HW);
     MD2_TRY(bn_bwd_partial_slabs(SlabIn{d.slab, d.splits}, da, y, bn.mean, bn.invstd, nimg, bn.p.c,
@@ -1517,6 +1531,9 @@ class Model {
     const float* mg = relu_from_y ? P(bn.p.g) : nullptr;
     const float* mb = relu_from_y ? P(bn.p.b) : nullptr;
     if (relu_from_y) mask = nullptr;
+    if (fuse_bn_bwd && bn_bwd_channel_fits(nimg, HW))   // layers 3-4 at the bench shape: one launch
+      return bn_bwd_channel(dout, SlabIn{}, mask, y, bn.mean, bn.invstd, P(bn.p.g), mb, Gd(bn.p.g),
+                            Gd(bn.p.b), nimg, bn.p.c, HW, dy, dres, dres_acc, st, sk);
     MD2_TRY(bn_bwd_partial(dout, mask, y, bn.mean, bn.invstd, nimg, bn.p.c, HW, w, st, mg, mb, sk));
     return bn_bwd_apply_fused(dout, mask, y, bn.mean, bn.invstd, P(bn.p.g), w, Gd(bn.p.g),
                               Gd(bn.p.b), nimg, bn.p.c, HW, dy, dres, dres_acc, st, mb, sk);

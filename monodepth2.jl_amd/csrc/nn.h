@@ -86,6 +86,17 @@ int bn_bwd_apply_fused(const float* dout, const float* mask_out, const float* y,
                        float* dbeta, int N, int C, long HW, float* dy, float* dres,
                        int dres_accumulate, hipStream_t st, const float* mbeta = nullptr,
                        SkipAdd sk = SkipAdd{});
+// The whole backward in one launch for a BN whose channel fits in a block (HW % 4 == 0 and
+// N*HW/4 float4 units within a 256-thread block's registers): partial sums, dgamma/dbeta and the
+// apply, each tensor read once.  dout, or sl (the dgrad's split-K slabs, summed in split order;
+// dout == nullptr, no mask_out / sk, nothing but dy written); mask_out / mbeta / sk / dres as in
+// the two passes.  The fp64 sums run in the block's own fixed order: last-bit differences to the
+// two passes at most.
+bool bn_bwd_channel_fits(int N, long HW);
+int bn_bwd_channel(const float* dout, SlabIn sl, const float* mask_out, const float* y,
+                   const float* mean, const float* invstd, const float* gamma, const float* mbeta,
+                   float* dgamma, float* dbeta, int N, int C, long HW, float* dy, float* dres,
+                   int dres_accumulate, hipStream_t st, SkipAdd sk = SkipAdd{});
 // dy = gamma*invstd*(g - dbeta/L - xhat*dgamma/L); optional dres (=g) store/accumulate
 int bn_bwd_apply(const float* dout, const float* mask_out, const float* y, const float* mean,
                  const float* invstd, const float* gamma, const float* dgamma,

@@ -850,6 +850,164 @@ int bn_bwd_apply_fused(const float* dout, const float* mask_out, const float* y,
   return MD2_OK;
 }
 
+// ---- whole BN backward in one kernel when a channel fits in a block: one 1024-thread block per
+// channel holds the channel's g (= dout [+ skip | summed from split-K slabs], ReLU-masked) and y
+// in registers -- BN_CH_UNITS float4 units per thread -- sums them, stores dgamma/dbeta and
+// applies, so each tensor is read once and the partials never leave the block.
+// The fp64 sums run in one fixed order for every form (a thread's units in order, wave
+// reduction, the waves in order): plain, SKIP and SLAB steps stay bit-identical to each other.  The
+// apply spells its roundings out (no contraction that could differ between instantiations).
+// Against the two-pass path the sums run in another order: dgamma/dbeta/dy agree to the last
+// bits, not bitwise (as MD2_FUSE_BNSTATS for the forward).
+// 16 waves x 2 units: 8192 values per channel.  (4 waves x 8 units left the split-K slab form at
+// 21-23 us per launch on layers 3-4, against 17.5: a round trip per split with 4 waves per CU to
+// hide it; the step measured 6.255 against 6.266 ms, profiles/bn_bwd_channel_ab.txt.)
+constexpr int BN_CH_THREADS = 1024;
+constexpr int BN_CH_UNITS = 2;
+
+template <bool SLAB, bool SKIP>
+__global__ __launch_bounds__(BN_CH_THREADS) void bn_bwd_channel_kernel(
+    const float* __restrict__ dout, const float* __restrict__ mask, const float* __restrict__ y,
+    const float* __restrict__ mean, const float* __restrict__ invstd,
+    const float* __restrict__ gamma, const float* __restrict__ mbeta, int C, int N, FastDiv fdu,
+    float invL, float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dy,
+    float* __restrict__ dres, int dres_acc, SlabIn sl, SkipSrc pd) {
+  static_assert(!(SLAB && SKIP), "SLAB: no skip addend (and no mask tensor)");
+  constexpr int NW = BN_CH_THREADS / 64;
+  __shared__ double red[2 * NW];
+  const int c = blockIdx.x;
+  const uint32_t U = fdu.d, HW = 4u * U, nu = (uint32_t)N * U;
+  const float mu = mean[c], is = invstd[c];
+  const YMask ym = ymask(gamma, mbeta, c, mu, is);
+  const long sstride = (long)C * N * HW;
+  float4 gv[BN_CH_UNITS], yv[BN_CH_UNITS];
+  uint32_t off[BN_CH_UNITS];
+  // every load of the channel in flight before the first is used
+#pragma unroll
+  for (int h = 0; h < BN_CH_UNITS; ++h) {
+    const uint32_t e = threadIdx.x + (uint32_t)BN_CH_THREADS * h;
+    gv[h] = yv[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    off[h] = 0;
+    if (e >= nu) continue;
+    const uint32_t im = fdiv(e, fdu), k = e - im * U;
+    const uint32_t i = (im * (uint32_t)C + (uint32_t)c) * HW + 4u * k;
+    off[h] = i;
+    if (!SLAB) gv[h] = *reinterpret_cast<const float4*>(dout + i);
+    if (SKIP) gv[h] = add_skip4(pd, i, gv[h]);
+    yv[h] = *reinterpret_cast<const float4*>(y + i);
+    if (mask) {
+      const float4 m = *reinterpret_cast<const float4*>(mask + i);
+      if (!(m.x > 0.f)) gv[h].x = 0.f;
+      if (!(m.y > 0.f)) gv[h].y = 0.f;
+      if (!(m.z > 0.f)) gv[h].z = 0.f;
+      if (!(m.w > 0.f)) gv[h].w = 0.f;
+    }
+  }
+  if (SLAB) {
+    // split by split, a split's units all in flight: each element still adds its slabs in split
+    // order from 0 (bn_bwd_partial_kernel<.., SLAB>'s order, the conv's own reduction)
+    const float* sq = sl.slab + (long)c * N * HW;
+    for (int q = 0; q < sl.splits; ++q, sq += sstride) {
+      float4 t[BN_CH_UNITS];
+#pragma unroll
+      for (int h = 0; h < BN_CH_UNITS; ++h) {
+        const uint32_t e = threadIdx.x + (uint32_t)BN_CH_THREADS * h;   // slab plane [N][HW]: 4 * e
+        if (e < nu) t[h] = *reinterpret_cast<const float4*>(sq + 4u * e);
+      }
+#pragma unroll
+      for (int h = 0; h < BN_CH_UNITS; ++h) {
+        if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+        gv[h].x += t[h].x; gv[h].y += t[h].y; gv[h].z += t[h].z; gv[h].w += t[h].w;
+      }
+    }
+  }
+  double sg = 0.0, sgx = 0.0;
+#pragma unroll
+  for (int h = 0; h < BN_CH_UNITS; ++h) {
+    if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+    float4& g = gv[h];
+    const float4 v = yv[h];
+    g.x = ymasked(g.x, v.x, ym);
+    g.y = ymasked(g.y, v.y, ym);
+    g.z = ymasked(g.z, v.z, ym);
+    g.w = ymasked(g.w, v.w, ym);
+    // (the fp64 product of two floats is exact: an fma contraction changes no bit)
+    sg += (double)g.x + (double)g.y + (double)g.z + (double)g.w;
+    sgx += (double)g.x * (double)((v.x - mu) * is) + (double)g.y * (double)((v.y - mu) * is) +
+           (double)g.z * (double)((v.z - mu) * is) + (double)g.w * (double)((v.w - mu) * is);
+  }
+  sg = wave_sum_d(sg);
+  sgx = wave_sum_d(sgx);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[wid] = sg;
+    red[NW + wid] = sgx;
+  }
+  __syncthreads();
+  double tg = red[0], tgx = red[NW];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+    tg += red[w];
+    tgx += red[NW + w];
+  }
+  const float dbf = (float)tg, dgf = (float)tgx;
+  if (threadIdx.x == 0) {
+    dbeta[c] = dbf;
+    dgamma[c] = dgf;
+  }
+  const float k0 = __fmul_rn(gamma[c], is), db = __fmul_rn(dbf, invL), dg = __fmul_rn(dgf, invL);
+#pragma unroll
+  for (int h = 0; h < BN_CH_UNITS; ++h) {
+    if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+    const uint32_t i = off[h];
+    const float g[4] = {gv[h].x, gv[h].y, gv[h].z, gv[h].w};
+    const float v[4] = {yv[h].x, yv[h].y, yv[h].z, yv[h].w};
+    float r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float xh = __fmul_rn(__fsub_rn(v[k], mu), is);
+      r[k] = __fmul_rn(k0, __fmaf_rn(-xh, dg, __fsub_rn(g[k], db)));
+    }
+    *reinterpret_cast<float4*>(dy + i) = make_float4(r[0], r[1], r[2], r[3]);
+    if (dres) {
+      float4 o = gv[h];
+      if (dres_acc) {
+        const float4 q = *reinterpret_cast<const float4*>(dres + i);
+        o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
+      }
+      *reinterpret_cast<float4*>(dres + i) = o;
+    }
+  }
+}
+
+bool bn_bwd_channel_fits(int N, long HW) {
+  return HW % 4 == 0 && (long)N * (HW / 4) <= (long)BN_CH_THREADS * BN_CH_UNITS;
+}
+
+int bn_bwd_channel(const float* dout, SlabIn sl, const float* mask_out, const float* y,
+                   const float* mean, const float* invstd, const float* gamma, const float* mbeta,
+                   float* dgamma, float* dbeta, int N, int C, long HW, float* dy, float* dres,
+                   int dres_accumulate, hipStream_t st, SkipAdd sk) {
+  const long n = (long)N * C * HW;
+  MD2_TRY(check_u31(n));
+  MD2_CHECK_ARG(bn_bwd_channel_fits(N, HW), "bn_bwd_channel: a channel must fit in a block");
+  MD2_CHECK_ARG((sl.slab != nullptr) != (dout != nullptr) &&
+                    (!sl.slab || (sl.splits >= 1 && !sk.skip && !mask_out)),
+                "bn_bwd_channel: dout or slabs (slabs without skip / mask tensor)");
+  MD2_CHECK_ARG(!sk.skip || (sk.lo >= 0 && sk.lo <= sk.hi && sk.hi <= n), "bn_bwd: skip range");
+  const float invL = 1.f / (float)((long)N * HW);
+#define MD2_BWDC(SL, SK)                                                                        \
+  hipLaunchKernelGGL((bn_bwd_channel_kernel<SL, SK>), dim3(C), dim3(BN_CH_THREADS), 0, st, dout, \
+                     mask_out, y, mean, invstd, gamma, mbeta, C, N, fd(HW / 4), invL, dgamma,    \
+                     dbeta, dy, dres, dres_accumulate, sl, skip_src(sk))
+  if (sl.slab) MD2_BWDC(true, false);
+  else if (sk.skip) MD2_BWDC(false, true);
+  else MD2_BWDC(false, false);
+#undef MD2_BWDC
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // MaxPool 3x3 / stride 2 / pad 1 (ResNet stem); argmax kept as the window index 0..8
 // ---------------------------------------------------------------------------------------------
