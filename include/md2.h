@@ -550,6 +550,70 @@ size_t md2_depth_eval_workspace_size(const md2_depth_eval_cfg* cfg);   /* 0 for 
 int md2_depth_eval(const md2_depth_eval_cfg* cfg, const float* disp, const float* gt,
                    float* metrics, int* counts, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ground-truth depth maps from LiDAR scans, and the flip post-processing of disparities -- the two
+ * steps around md2_depth_eval in a Monodepth2-style evaluation.  Additive: MD2_ABI_VERSION is
+ * unchanged.
+ *
+ * md2_lidar_depth rasterises n Velodyne scans into n depth maps [h][w]: project, round, "minus
+ * one", nearest point wins.  Scan i is points[offsets[i] .. offsets[i+1]-1], four fp32 values per
+ * point (x, y, z, reflectance; the last is ignored), points 16-byte aligned; p = P[i] is its
+ * row-major 3x4 velodyne -> image matrix (KITTI: P_rect * R_rect * [R|T]).  offsets and P are HOST
+ * arrays, read before the call returns.  For each point (X, Y, Z), all arithmetic in fp32, each
+ * operation rounded on its own (no fused multiply-add):
+ *  1. x = ((p0*X + p1*Y) + p2*Z) + p3;  y likewise from p4..p7;  zc from p8..p11.
+ *  2. u = x / zc, v = y / zc, correctly rounded divisions.
+ *  3. ix = (int)rintf(u) - 1, iy = (int)rintf(v) - 1 (ties to even; the -1 is the KITTI devkit's
+ *     1-based pixel convention, which Monodepth2 keeps).
+ *  4. The stored value s = vel_depth ? X : zc.
+ *  5. The point is DROPPED if forward_only && X < 0; or s is not finite and > 0; or zc is not finite
+ *     and > 0; or u or v is not finite; or (ix, iy) is outside [0, w) x [0, h) -- tested on the
+ *     rounded floats, before the conversion to int, so a huge u cannot wrap into the image.
+ *  6. depth[i][iy][ix] = the minimum s over the points that land there; a pixel no point lands in
+ *     is 0.0f ("no measurement", as md2_depth_eval reads it).
+ *  7. counts[i] = {points not dropped, pixels != 0}; counts may be NULL.
+ * An empty scan (offsets[i] == offsets[i+1]) gives an all-zero map.  Two departures from
+ * Monodepth2's generate_depth_map: that script multiplies a float64 matrix with float32 points,
+ * and lets a negative depth win the minimum before zeroing it; here everything is fp32 and a
+ * non-positive value never competes.  To rasterise at a size other than the camera's, scale rows
+ * 0 and 1 of P.
+ * The minimum is an integer atomicMin on the bit pattern (positive finite floats order as unsigned
+ * integers) and the counts are integer atomics, so the result is BITWISE REPRODUCIBLE and
+ * independent of the order the points arrive in.  The call enqueues a fill, a scatter pass and a
+ * finishing pass on `stream`; it allocates nothing, needs no workspace and never synchronises with
+ * the host.  offsets and P ride in the scatter kernel's argument block (3.3 KB at 64 scans: the
+ * reason for the cap; callers chunk larger batches).
+ * MD2_EINVAL (checked before any HIP call): a null cfg, offsets, P or depth; null points unless
+ * offsets[n] == 0; points not 16-byte aligned; n outside 1..MD2_LIDAR_MAX_SCANS; h or w < 1 or
+ * h * w > 2^24; offsets[0] < 0, a decreasing offset or offsets[n] > 2^27; a non-finite entry of P;
+ * forward_only or vel_depth not 0 or 1.
+ *
+ * md2_disp_post_process blends the disparity of a frame, disp [n][h][w], with the network's output
+ * for the horizontally mirrored frame, disp_flipped (as produced: NOT mirrored back), as Monodepth
+ * and Monodepth2 do for their "+pp" rows.  At (y, x), in fp32 in this order without contraction:
+ *   l = disp[y][x],  r = disp_flipped[y][w-1-x],  t(x) = w > 1 ? (float)x / (float)(w-1) : 0,
+ *   ml = 1 - fminf(fmaxf(20 * (t(x) - 0.05f), 0), 1),  mr = the same at w-1-x,
+ *   out = (mr*l + ml*r) + ((1 - ml) - mr) * (0.5f * (l + r)).
+ * out may alias disp; it must not alias disp_flipped (MD2_EINVAL when the pointers are equal, as
+ * for a null pointer or a size < 1).
+ * ---------------------------------------------------------------------------------------- */
+#define MD2_LIDAR_MAX_SCANS 64
+typedef struct md2_lidar_cfg {
+  int n;               /* scans = depth maps, 1..MD2_LIDAR_MAX_SCANS                    */
+  int h, w;            /* depth-map size                                               */
+  int forward_only;    /* 1: drop points with x_velo < 0 (Monodepth2)                  */
+  int vel_depth;       /* 1: store x_velo instead of the camera z                      */
+} md2_lidar_cfg;
+int md2_lidar_depth(const md2_lidar_cfg* cfg,
+                    const float* points,        /* device [total][4]: x, y, z, reflectance (ignored) */
+                    const long long* offsets,   /* HOST [n+1]: scan i = points offsets[i] .. offsets[i+1]-1 */
+                    const float* P,             /* HOST [n][12]: row-major 3x4 velodyne -> image, per scan */
+                    float* depth,               /* device [n][h][w]; 0 = no measurement         */
+                    int* counts,                /* device [n][2] = {points stored, pixels hit}; NULL ok */
+                    void* stream);
+int md2_disp_post_process(const float* disp, const float* disp_flipped, int n, int h, int w,
+                          float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,12 @@ struct DepthEvalCfg                                    # md2_depth_eval_cfg
     scale::Cfloat
 end
 
+struct LidarCfg                                        # md2_lidar_cfg
+    n::Cint; h::Cint; w::Cint
+    forward_only::Cint
+    vel_depth::Cint
+end
+
 # ------------------------------------------------------------------------------------------------
 # The model: Model(ResidualNetwork, DepthDecoder, PoseDecoder) with its parameters in ONE flat
 # device vector (Flux `params(model)` order, md2_arch_param_info) -- src/model.jl:24-70
@@ -707,6 +713,41 @@ function depth_errors(disp::ROCArray{Float32}, gt::ROCArray{Float32,3}; crop=:ga
                 (Ref{DepthEvalCfg}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Cvoid}),
                 cfg, disp, gt, metrics, counts, ws, stream_ptr()))
     return metrics, counts
+end
+
+# Ground-truth depth maps from LiDAR scans (include/md2.h states every operation): points (4, M)
+# = x, y, z, reflectance per column; offsets: n+1 0-based host offsets, scan i = columns
+# offsets[i]+1 .. offsets[i+1]; P: the row-major 3x4 velodyne -> image matrices as the C side reads
+# them, i.e. (4, 3, n) in Julia's column-major order (permutedims of the usual 3x4), or (4, 3) for
+# all scans.  Returns depth (w, h, n) on the device, 0 = no measurement; with return_counts also
+# counts (2, n) = points stored, pixels hit.  At most LIDAR_MAX_SCANS scans per call.  No host sync.
+const LIDAR_MAX_SCANS = 64
+function lidar_depth(points::ROCArray{Float32,2}, offsets::Vector{Int64}, P::Array{Float32}, h, w;
+                     forward_only=true, vel_depth=false, return_counts=false)
+    size(points, 1) == 4 || error("points must be (4, M)")
+    n = length(offsets) - 1
+    1 <= n <= LIDAR_MAX_SCANS || error("1..", LIDAR_MAX_SCANS, " scans per call, got ", n)
+    ndims(P) == 2 && (P = repeat(reshape(P, 4, 3, 1), 1, 1, n))
+    size(P) == (4, 3, n) || error("P must be (4, 3) or (4, 3, ", n, ")")
+    offsets[end] <= size(points, 2) || error("offsets end past the points")
+    cfg = LidarCfg(n, h, w, forward_only ? 1 : 0, vel_depth ? 1 : 0)
+    depth = ROCArray{Float32}(undef, w, h, n); counts = ROCArray{Int32}(undef, 2, n)
+    check(ccall((:md2_lidar_depth, lib), Cint,
+                (Ref{LidarCfg}, Ptr{Float32}, Ptr{Clonglong}, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+                cfg, points, offsets, P, depth, counts, stream_ptr()))
+    return return_counts ? (depth, counts) : depth
+end
+
+# Monodepth's flip post-processing ("+pp"): disp (w,h,n) or (w,h,1,n) blended with disp_flipped,
+# the network's output for the horizontally mirrored frame as produced (not mirrored back).
+function post_process_disparity(disp::ROCArray{Float32}, disp_flipped::ROCArray{Float32})
+    (ndims(disp) == 3 || (ndims(disp) == 4 && size(disp, 3) == 1)) || error("disp must be (w,h,n) or (w,h,1,n)")
+    size(disp) == size(disp_flipped) || error("disp_flipped must have disp's size")
+    out = similar(disp)
+    check(ccall((:md2_disp_post_process, lib), Cint,
+                (Ptr{Float32}, Ptr{Float32}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Cvoid}),
+                disp, disp_flipped, size(disp, ndims(disp)), size(disp, 2), size(disp, 1), out, stream_ptr()))
+    return out
 end
 
 function find_static(dataset, α; batch=16)

@@ -14,6 +14,8 @@ from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .data import DataLoader, DChain, Depth10k, FlipX, KittyDataset, find_static  # noqa: F401
 from .mpi import MPIDepthDecoder, mpi_forward  # noqa: F401
 from .evaluate import METRIC_NAMES, depth_errors, evaluate_depth, garg_crop  # noqa: F401
+from .lidar import (kitti_odometry_velo_to_image, kitti_raw_velo_to_image, lidar_depth, load_velodyne,  # noqa: F401
+                    post_process_disparity)
 
 __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_poses", "lib", "MD2Error",
            "ADAM", "DepthDecoder", "Model", "Pose", "PoseDecoder", "ResidualNetwork", "ResNet",
@@ -22,4 +24,6 @@ __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_pos
            "SlowDepth", "adam_update", "slow_depth", "load_checkpoint", "save_checkpoint",
            "DataLoader", "DChain", "Depth10k", "FlipX", "KittyDataset", "find_static",
            "MPIDepthDecoder", "mpi_forward",
-           "METRIC_NAMES", "depth_errors", "evaluate_depth", "garg_crop"]
+           "METRIC_NAMES", "depth_errors", "evaluate_depth", "garg_crop",
+           "kitti_odometry_velo_to_image", "kitti_raw_velo_to_image", "lidar_depth", "load_velodyne",
+           "post_process_disparity"]

@@ -83,6 +83,14 @@ class DepthEvalCfg(C.Structure):
     ]
 
 
+LIDAR_MAX_SCANS = 64     # include/md2.h MD2_LIDAR_MAX_SCANS
+
+
+class LidarCfg(C.Structure):
+    """``md2_lidar_cfg``."""
+    _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("forward_only", C.c_int), ("vel_depth", C.c_int)]
+
+
 _lib = None
 _load_error = None
 
@@ -162,6 +170,8 @@ _SIGS = {
     "md2_model_testmode": (C.c_int, [P]),
     "md2_depth_eval_workspace_size": (C.c_size_t, [C.POINTER(DepthEvalCfg)]),
     "md2_depth_eval": (C.c_int, [C.POINTER(DepthEvalCfg), P, P, P, P, P, P]),
+    "md2_lidar_depth": (C.c_int, [C.POINTER(LidarCfg), P, C.POINTER(C.c_longlong), C.POINTER(C.c_float), P, P, P]),
+    "md2_disp_post_process": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
     "md2_model_debug_tensor": (C.c_int, [P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int)]),
     "md2_model_features": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),

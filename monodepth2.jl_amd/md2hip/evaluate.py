@@ -76,12 +76,15 @@ def depth_errors(disp, gt, *, crop="garg", min_depth=0.1, max_depth=100.0, eval_
     return metrics, counts
 
 
-def evaluate_depth(model, batches, *, allow_nonfinite=False, **depth_errors_kwargs):
+def evaluate_depth(model, batches, *, allow_nonfinite=False, post_process=False, **depth_errors_kwargs):
     """Score ``model`` over ``batches``, an iterable of ``(x [n, C, H, W], gt [n, Hg, Wg])`` device
     pairs: ``md2hip.eval_disparity(model, x)`` in whatever mode the model is in -- call
     ``model.testmode()`` first, so that BatchNorm uses its running statistics and an image's score
     does not depend on its batch -- then ``depth_errors`` on the last (full-resolution) level.
-    Everything accumulates on the device; the host syncs once at the end.
+    Everything accumulates on the device; the host syncs once at the end.  ``post_process=True``
+    scores Monodepth's flip post-processing instead ("+pp"): each batch is also predicted mirrored,
+    ``eval_disparity(model, x.flip(-1))``, and the two disparities are blended by
+    ``post_process_disparity``.
 
     Returns a dict: the mean over the images with ``count > 0`` of ``abs_rel, sq_rel, rmse,
     rmse_log, a1, a2, a3``; ``ratio_median`` and ``ratio_std`` (the standard deviation of
@@ -92,12 +95,18 @@ def evaluate_depth(model, batches, *, allow_nonfinite=False, **depth_errors_kwar
     ``fmaxf(v, 0)``, which turns a NaN into 0, so a NaN pixel yields a finite, meaningless disparity.
     ``n_bad > 0`` or ``nonfinite_inputs > 0`` raises ``RuntimeError`` unless ``allow_nonfinite``."""
     import torch
+    from .lidar import post_process_disparity
     from .model import eval_disparity
     ms, cs, bad_in = [], [], None
     for x, gt in batches:
         nf = (~torch.isfinite(x)).sum()                     # stays on the device
         bad_in = nf if bad_in is None else bad_in + nf
         disp = eval_disparity(model, x)[-1]
+        if post_process:
+            # eval_disparity returns views of executor-owned buffers that the next call overwrites:
+            # the first result is cloned before the mirrored frame runs, and the blend lands in the clone
+            disp = disp.clone()
+            post_process_disparity(disp, eval_disparity(model, x.flip(-1))[-1], out=disp)
         m, c = depth_errors(disp, gt, **depth_errors_kwargs)
         ms.append(m)
         cs.append(c)
