@@ -614,6 +614,83 @@ int md2_lidar_depth(const md2_lidar_cfg* cfg,
 int md2_disp_post_process(const float* disp, const float* disp_flipped, int n, int h, int w,
                           float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Colour augmentation of a training batch, and a training forward with a separate network input.
+ * Monodepth2 jitters the frames the encoder and the pose network see and computes the photometric
+ * loss, SSIM and the automask on the ORIGINAL frames.  Additive: MD2_ABI_VERSION is unchanged.
+ *
+ * md2_color_jitter applies torchvision's float-tensor ColorJitter to x [n][frames][c][h][w], c = 1
+ * or 3, into out (same layout).  params[i] (a HOST array, read before the call returns) holds sample
+ * i's four factors, the order of the four operations and whether the sample is changed at all; the
+ * same parameters apply to every frame of the sample.  All arithmetic is fp32, each operation
+ * rounded on its own (no fused multiply-add; divisions correctly rounded).  With
+ *   clamp(v) = fminf(fmaxf(v, 0), 1),   blend(a, b, t) = clamp(t*a + (1 - t)*b),
+ *   gray = (0.2989f*r + 0.587f*g) + 0.114f*b     (c == 1: the value itself),
+ * the operations, applied to a pixel in the order order[0..3], are
+ *  0 brightness  v = clamp(brightness * v) per channel.
+ *  1 contrast    v = blend(v, mean, contrast) per channel; mean is the mean of gray over the FRAME
+ *                (per frame, as torchvision; not per sample) as it stands when contrast is applied,
+ *                i.e. after the operations that precede it in order: mean = (float)(S / (double)(h*w)),
+ *                S the fp64 sum of the fp32 gray values in the fixed order given below.
+ *                means[i][f] receives it (0 for a sample with apply == 0); means may be NULL.
+ *  2 saturation  v = blend(v, gray, saturation) per channel; the identity for c == 1.
+ *  3 hue         the identity for c == 1; otherwise
+ *     1. mx, mn = the channel max and min;  eq = (mx == mn);  cr = mx - mn.
+ *     2. s = cr / (eq ? 1 : mx);  d = eq ? 1 : cr.
+ *     3. rc = (mx - r) / d,  gc = (mx - g) / d,  bc = (mx - b) / d.
+ *     4. hh = (mx == r) ? bc - gc : (mx == g) ? (2 + rc) - bc : (4 + gc) - rc.
+ *     5. t = hh / 6 + 1;  hh = t - floorf(t).
+ *     6. t = hh + hue;    hh = t - floorf(t).
+ *     7. h6 = hh * 6;  i = floorf(h6);  f = h6 - i;  i = (int)i % 6.
+ *     8. p = clamp(mx * (1 - s)),  q = clamp(mx * (1 - s*f)),  tt = clamp(mx * (1 - s*(1 - f))).
+ *     9. (r, g, b) = (mx,tt,p), (q,mx,p), (p,mx,tt), (p,q,mx), (tt,p,mx), (mx,p,q) for i = 0..5.
+ *    hh may come out as exactly 1.0; then i is 6 -> 0 and f = 0, which is continuous.
+ * A sample with apply == 0 is copied bit for bit.
+ * The sum S: with B = min(ceil(h*w / 1024), 64) blocks of 256 threads per frame, thread t of block k
+ * adds the gray of pixels (k*256 + t) + j * (B*256), j ascending, in fp64; the 64 lanes of a wave
+ * are combined by a butterfly (partner lane ^ 32, 16, 8, 4, 2, 1), the block's four waves as
+ * (w0 + w1) + (w2 + w3), and the frame's B block sums one after the other, k ascending.  A first
+ * launch forms the block sums in the workspace, a second adds them, recomputes the chain from x
+ * and writes out.  No floating-point atomics, and a grid that depends on the sizes alone: the
+ * result is BITWISE REPRODUCIBLE.  The call enqueues the two launches on `stream`; it allocates
+ * nothing, never synchronises with the host, and writes everything it reads of the workspace
+ * (md2_color_jitter_workspace_size bytes of 8-byte-aligned device memory, any content; the size
+ * is 0 for invalid sizes).  params rides in the kernels' argument block (1.3 KB at
+ * MD2_JITTER_MAX_SAMPLES: the reason for the cap; callers chunk larger batches).
+ * out == x is allowed (in place).
+ * MD2_EINVAL (checked before any HIP call): a null x, out, params or workspace; n, frames, h or
+ * w < 1; n > MD2_JITTER_MAX_SAMPLES; frames > 65535; c not 1 or 3; h * w > 2^24; a workspace that
+ * is not 8-byte aligned; order not a permutation of 0..3; a non-finite factor; a negative
+ * brightness, contrast or saturation; |hue| > 0.5; apply not 0 or 1; out overlapping x without
+ * being equal to it.
+ *
+ * md2_model_forward_loss_aug / md2_model_train_step_graph_aug are md2_model_forward_loss /
+ * md2_model_train_step_graph with a second input x_net, laid out as x: the encoder (and so both
+ * decoders) runs on x_net and the stem's filter gradient reads x_net back; the automask and the
+ * loss tail (warp, SSIM, L1) read x.  x_net == NULL or x_net == x IS the plain call (which is
+ * implemented as this one with x_net = x).  The result equals, bit for bit, md2_model_forward(x_net)
+ * followed by md2_loss_fwd_bwd on x (sigmoid_grad = 0) and md2_model_backward_from.  The backward
+ * segments, md2_model_backward_allreduce and md2_model_adam* follow either unchanged.  The graph
+ * variant copies x_net into a second executor-owned buffer each call and re-captures when the
+ * presence of x_net changes.  Test mode: MD2_ESTATE, as every training entry.  MPI mode
+ * (embedding_levels > 0) with a non-null x_net: MD2_ENOTSUP.
+ * ---------------------------------------------------------------------------------------- */
+#define MD2_JITTER_MAX_SAMPLES 64
+typedef struct md2_jitter {      /* one per sample, HOST array, read before the call returns */
+  float brightness, contrast, saturation, hue;  /* factors; hue is a shift in turns, |hue| <= 0.5 */
+  unsigned char order[4];        /* a permutation of 0 brightness, 1 contrast, 2 saturation, 3 hue */
+  int apply;                     /* 0: the sample is copied unchanged */
+} md2_jitter;
+size_t md2_color_jitter_workspace_size(int n, int frames, int h, int w);
+int md2_color_jitter(const float* x, int n, int frames, int c, int h, int w,
+                     const md2_jitter* params, float* out, float* means /* [n][frames] or NULL */,
+                     void* workspace, void* stream);
+int md2_model_forward_loss_aug(md2_model* m, const float* x, const float* x_net,
+                               const float* auto_loss, float* loss, float* terms, void* stream);
+int md2_model_train_step_graph_aug(md2_model* m, const float* x, const float* x_net,
+                                   const float* auto_loss, float* adam_m, float* adam_v,
+                                   float lr, int step, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

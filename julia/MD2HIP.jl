@@ -105,6 +105,12 @@ struct LidarCfg                                        # md2_lidar_cfg
     vel_depth::Cint
 end
 
+struct Jitter                                          # md2_jitter
+    brightness::Cfloat; contrast::Cfloat; saturation::Cfloat; hue::Cfloat
+    order::NTuple{4, Cuchar}
+    apply::Cint
+end
+
 # ------------------------------------------------------------------------------------------------
 # The model: Model(ResidualNetwork, DepthDecoder, PoseDecoder) with its parameters in ONE flat
 # device vector (Flux `params(model)` order, md2_arch_param_info) -- src/model.jl:24-70
@@ -305,11 +311,15 @@ model was built with (md2_model_cfg): any field that differs raises (`check_conf
 Zygote: `gradient(() -> train_loss(m, x, ...)[1], Flux.params(m))` (the implicit-parameter loop
 of scripts/script.jl:84-86, src/simple_depth.jl:25-42) returns the gradient under `m.θ`, in
 m.θ's own layout, so `Flux.Optimise.update!(opt, Flux.params(m), ∇)` updates m.θ consistently.
+
+`x_net` (like x, e.g. `color_jitter(x, params)`): the frames the networks see; the loss, SSIM and
+the automask stay on x (md2_model_forward_loss_aug).  `nothing`: the plain call.
 """
 function train_loss(m::HIPModel, x::ROCArray{Float32,5}, auto_loss, cache, params,
-                    do_visualization::Bool=false)
+                    do_visualization::Bool=false; x_net=nothing)
     check_config(m, cache, params)
-    _train_loss(m, m.θ, x, auto_loss, do_visualization)     # m.θ read in traced code: accum_param
+    x_net === nothing || size(x_net) == size(x) || error("x_net must have x's size")
+    _train_loss(m, m.θ, x, auto_loss, do_visualization, x_net)     # m.θ read in traced code: accum_param
 end
 
 # The executor's kernels, buffers and loss-tail weights are built for ONE (Params, TrainCache)
@@ -334,13 +344,19 @@ function check_config(m::HIPModel, cache, params)
 end
 
 function _train_loss(m::HIPModel, θ::ROCVector{Float32}, x::ROCArray{Float32,5}, auto_loss,
-                     do_visualization::Bool)
+                     do_visualization::Bool, x_net=nothing)
     θ === m.θ || error("train_loss: θ must be the model's own parameter vector")
     m.packed || repack!(m)               # θ may have been updated in place since the last step
     loss = ROCVector{Float32}(undef, 1)
-    check(ccall((:md2_model_forward_loss, lib), Cint,
-                (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
-                m.handle, x, ptr(auto_loss), loss, C_NULL, stream_ptr()))
+    if x_net === nothing
+        check(ccall((:md2_model_forward_loss, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                    m.handle, x, ptr(auto_loss), loss, C_NULL, stream_ptr()))
+    else
+        check(ccall((:md2_model_forward_loss_aug, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                    m.handle, x, x_net, ptr(auto_loss), loss, C_NULL, stream_ptr()))
+    end
     l = Array(loss)[1]                   # host scalar, as the reference's mean(...) / T(...)
     do_visualization || return (l, nothing, nothing, nothing)
     disps, pose = outputs(m)
@@ -383,8 +399,8 @@ end
 # expected to update θ next, so the packed weights are marked stale (re-packed by the next
 # train_loss, or already by the library's own update!).
 function ChainRulesCore.rrule(::typeof(_train_loss), m::HIPModel, θ::ROCVector{Float32}, x, auto_loss,
-                              do_visualization::Bool)
-    y = _train_loss(m, θ, x, auto_loss, do_visualization)
+                              do_visualization::Bool, x_net=nothing)
+    y = _train_loss(m, θ, x, auto_loss, do_visualization, x_net)
     function train_loss_pullback(Δ)
         Δl = unthunk(Δ[1])
         Δl = Δl isa AbstractZero ? 0f0 : Float32(Δl)
@@ -392,7 +408,7 @@ function ChainRulesCore.rrule(::typeof(_train_loss), m::HIPModel, θ::ROCVector{
                     m.handle, Δl, stream_ptr()))
         gradient!(m)
         m.packed = false
-        return (NoTangent(), NoTangent(), copy(m.∇θ), NoTangent(), NoTangent(), NoTangent())
+        return (NoTangent(), NoTangent(), copy(m.∇θ), NoTangent(), NoTangent(), NoTangent(), NoTangent())
     end
     return y, train_loss_pullback
 end
@@ -750,6 +766,27 @@ function post_process_disparity(disp::ROCArray{Float32}, disp_flipped::ROCArray{
     return out
 end
 
+# Colour augmentation (torchvision's ColorJitter; include/md2.h states every operation): x
+# (w,h,c,frames,n) with c = 1 or 3, params one Jitter per sample (factors, the order of the four
+# operations as 0 brightness, 1 contrast, 2 saturation, 3 hue, and apply = 0 to copy the sample).
+# Returns the jittered frames -- the x_net of train_loss; with return_means also the (frames, n)
+# contrast means.  out may be x (in place).  At most JITTER_MAX_SAMPLES samples per call.  No host sync.
+const JITTER_MAX_SAMPLES = 64
+function color_jitter(x::ROCArray{Float32,5}, params::Vector{Jitter}; out=similar(x), return_means=false)
+    w, h, c, frames, n = size(x)
+    length(params) == n || error("one Jitter per sample: ", n, ", got ", length(params))
+    1 <= n <= JITTER_MAX_SAMPLES || error("1..", JITTER_MAX_SAMPLES, " samples per call, got ", n)
+    size(out) == size(x) || error("out must have x's size")
+    ws = ROCVector{Float64}(undef, cld(ccall((:md2_color_jitter_workspace_size, lib), Csize_t,
+                                             (Cint, Cint, Cint, Cint), n, frames, h, w), 8))
+    means = ROCArray{Float32}(undef, frames, n)
+    check(ccall((:md2_color_jitter, lib), Cint,
+                (Ptr{Float32}, Cint, Cint, Cint, Cint, Cint, Ptr{Jitter}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid},
+                 Ptr{Cvoid}),
+                x, n, frames, c, h, w, params, out, means, ws, stream_ptr()))
+    return return_means ? (out, means) : out
+end
+
 function find_static(dataset, α; batch=16)
     keep = String[]
     for b0 in 1:batch:length(dataset)
@@ -763,13 +800,20 @@ end
 
 # One whole step (forward, loss, backward, ADAM(η) with β = (0.9, 0.999), ϵ = 1e-8) replayed as a
 # captured hipGraph; the same kernels in the same order as train_loss + gradient! + update!
-function train_step_graph!(m::HIPModel, x::ROCArray{Float32,5}, auto_loss, η)
+function train_step_graph!(m::HIPModel, x::ROCArray{Float32,5}, auto_loss, η; x_net=nothing)
     m.packed || repack!(m)
     m.step += 1; loss = ROCVector{Float32}(undef, 1)
-    check(ccall((:md2_model_train_step_graph, lib), Cint,
-                (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cint,
-                 Ptr{Float32}, Ptr{Cvoid}),
-                m.handle, x, ptr(auto_loss), m.m, m.v, η, m.step, loss, stream_ptr()))
+    if x_net === nothing
+        check(ccall((:md2_model_train_step_graph, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cint,
+                     Ptr{Float32}, Ptr{Cvoid}),
+                    m.handle, x, ptr(auto_loss), m.m, m.v, η, m.step, loss, stream_ptr()))
+    else
+        check(ccall((:md2_model_train_step_graph_aug, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cfloat, Cint,
+                     Ptr{Float32}, Ptr{Cvoid}),
+                    m.handle, x, x_net, ptr(auto_loss), m.m, m.v, η, m.step, loss, stream_ptr()))
+    end
     return loss
 end
 

@@ -457,6 +457,12 @@ int md2_model_forward_loss(md2_model* m, const float* x, const float* auto_loss,
   return model_forward_loss(m->impl, x, auto_loss, loss, terms, (hipStream_t)stream);
 }
 
+int md2_model_forward_loss_aug(md2_model* m, const float* x, const float* x_net, const float* auto_loss,
+                               float* loss, float* terms, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_forward_loss_aug(m->impl, x, x_net, auto_loss, loss, terms, (hipStream_t)stream);
+}
+
 int md2_model_forward(md2_model* m, const float* x, const float** disp, const float** pose,
                       void* stream) {
   MD2_CHECK_ARG(m, "model");
@@ -533,6 +539,13 @@ int md2_model_train_step_graph(md2_model* m, const float* x, const float* auto_l
   MD2_CHECK_ARG(m, "model");
   return model_train_step_graph(m->impl, x, auto_loss, adam_m, adam_v, lr, step, loss,
                                 (hipStream_t)stream);
+}
+
+int md2_model_train_step_graph_aug(md2_model* m, const float* x, const float* x_net, const float* auto_loss,
+                                   float* adam_m, float* adam_v, float lr, int step, float* loss, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_train_step_graph_aug(m->impl, x, x_net, auto_loss, adam_m, adam_v, lr, step, loss,
+                                    (hipStream_t)stream);
 }
 
 int md2_model_set_params(md2_model* m, const float* flux, void* stream) {

@@ -402,11 +402,12 @@ class Model {
   struct StepGraph {
     hipGraphExec_t exec = nullptr;
     hipStream_t st = nullptr;
-    float *x = nullptr, *autoloss = nullptr, *loss = nullptr, *bc = nullptr;
+    float *x = nullptr, *x_net = nullptr, *autoloss = nullptr, *loss = nullptr, *bc = nullptr;
     int* step = nullptr;
     float *adam_m = nullptr, *adam_v = nullptr;
     float lr = 0.f;
     int with_auto = -1;
+    int with_net = -1;   // a separate network input (train_step_graph_aug) is part of the capture
     int next_step = -1;
   } g;
 
@@ -1344,9 +1345,10 @@ class Model {
     return MD2_OK;
   }
 
-  int forward_loss(const float* x, const float* automask, float* loss, float* terms,
+  // x_net feeds the networks; the automask and the loss tail read x (x_net == x: the plain step)
+  int forward_loss(const float* x, const float* x_net, const float* automask, float* loss, float* terms,
                    hipStream_t st) {
-    MD2_TRY(forward(x, st));
+    MD2_TRY(forward(x_net, st));
     const float* disps[MAX_SCALES] = {};
     LossTailOut o{};
     int li = 0;
@@ -1868,14 +1870,28 @@ static int refuse_testmode(const Model* m, const char* what) {
   return MD2_ESTATE;
 }
 
-int model_forward_loss(Model* m, const float* x, const float* automask, float* loss, float* terms,
-                       hipStream_t st) {
+// a separate network input is not wired through the MPI-mode plane replication
+static int refuse_mpi_net(const Model* m, const float* x_net, const char* what) {
+  if (!x_net || m->E == 0) return MD2_OK;
+  set_error(std::string(what) + ": x_net is not supported in MPI mode (embedding_levels > 0)");
+  return MD2_ENOTSUP;
+}
+
+int model_forward_loss_aug(Model* m, const float* x, const float* x_net, const float* automask, float* loss,
+                           float* terms, hipStream_t st) {
   MD2_CHECK_ARG(m && x, "model/x");
   MD2_TRY(refuse_testmode(m, "forward_loss"));
+  MD2_TRY(refuse_mpi_net(m, x_net, "forward_loss_aug"));
+  if (!x_net) x_net = x;
   MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
-  m->cur_x = x;
+  m->cur_x = x_net;            // the stem's filter gradient reads what the stem's forward read
   m->cot_ready = 1;
-  return m->forward_loss(x, automask, loss, terms, st);
+  return m->forward_loss(x, x_net, automask, loss, terms, st);
+}
+
+int model_forward_loss(Model* m, const float* x, const float* automask, float* loss, float* terms,
+                       hipStream_t st) {
+  return model_forward_loss_aug(m, x, nullptr, automask, loss, terms, st);
 }
 
 int model_forward(Model* m, const float* x, hipStream_t st) {
@@ -1904,11 +1920,12 @@ int model_num_segments(Model* m) { return m ? 6 : 0; }
 // ---------------------------------------------------------------------------------------------
 // Graph-captured train step (forward + loss + every backward segment + ADAM + weight repack as
 // ONE hipGraph): the ~320 launches of a step replay without per-launch host work.  Captured on
-// the executor's own stream on first use (and again when adam_m / adam_v / lr / the automask
-// input change); each call copies x (and auto_loss) into the executor's input buffers, replays
+// the executor's own stream on first use (and again when adam_m / adam_v / lr / the presence of
+// the automask input or of x_net change); each call copies x (and auto_loss, x_net) into the
+// executor's input buffers, replays
 // on `st`, and copies the loss out.  ADAM's step count lives on the device (adam_prep), re-set
 // only when the caller's `step` is not the one the graph expects next.
-static int capture_step(Model* m, bool with_auto, float* adam_m, float* adam_v, float lr) {
+static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, float* adam_v, float lr) {
   auto& g = m->g;
   if (g.exec) {
     MD2_HIP(hipGraphExecDestroy(g.exec));
@@ -1925,11 +1942,14 @@ static int capture_step(Model* m, bool with_auto, float* adam_m, float* adam_v, 
     MD2_TRY(m->alloc(&q, 4));
     g.step = (int*)q;
   }
+  if (with_net && !g.x_net)
+    MD2_TRY(m->alloc(&g.x_net, (long)m->N * 3 * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W));
+  const float* net = with_net ? g.x_net : g.x;
   MD2_HIP(hipStreamBeginCapture(g.st, hipStreamCaptureModeThreadLocal));
   auto body = [&]() -> int {
-    m->cur_x = g.x;
+    m->cur_x = net;
     m->cot_ready = 1;
-    MD2_TRY(m->forward_loss(g.x, with_auto ? g.autoloss : nullptr, g.loss, nullptr, g.st));
+    MD2_TRY(m->forward_loss(g.x, net, with_auto ? g.autoloss : nullptr, g.loss, nullptr, g.st));
     for (int k = 0; k < model_num_segments(m); ++k) MD2_TRY(model_backward_segment(m, k, nullptr, nullptr, g.st));
     MD2_TRY(adam_prep(g.step, g.bc, 0.9f, 0.999f, g.st));
     MD2_TRY(adam_step_dev(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, 0.9f, 0.999f, 1e-8f,
@@ -1951,38 +1971,49 @@ static int capture_step(Model* m, bool with_auto, float* adam_m, float* adam_v, 
   g.adam_v = adam_v;
   g.lr = lr;
   g.with_auto = with_auto ? 1 : 0;
+  g.with_net = with_net ? 1 : 0;
   g.next_step = -1;
   return MD2_OK;
 }
 
-int model_train_step_graph(Model* m, const float* x, const float* auto_loss, float* adam_m,
-                           float* adam_v, float lr, int step, float* loss, hipStream_t st) {
+int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, const float* auto_loss,
+                               float* adam_m, float* adam_v, float lr, int step, float* loss, hipStream_t st) {
   MD2_CHECK_ARG(m && x && adam_m && adam_v && loss && step >= 1, "train_step_graph args");
   MD2_TRY(refuse_testmode(m, "train_step_graph"));
+  MD2_TRY(refuse_mpi_net(m, x_net, "train_step_graph_aug"));
+  if (x_net == x) x_net = nullptr;   // the plain step: one input buffer, the plain capture
   auto& g = m->g;
   const bool with_auto = auto_loss != nullptr;
+  const bool with_net = x_net != nullptr;
   if (m->prof) {   // per-launch HIP events cannot live in a replayed graph: eager step
-    MD2_TRY(model_forward_loss(m, x, auto_loss, loss, nullptr, st));
+    MD2_TRY(model_forward_loss_aug(m, x, x_net, auto_loss, loss, nullptr, st));
     for (int k = 0; k < model_num_segments(m); ++k) MD2_TRY(model_backward_segment(m, k, nullptr, nullptr, st));
     return model_adam(m, adam_m, adam_v, lr, 0.9f, 0.999f, 1e-8f, step, 1.f, st);
   }
   // the replay reads and writes params, adam_m / adam_v and the packed weights: order it after
   // pending per-segment updates (outside the capture: the event lives outside the graph)
   MD2_TRY(m->adam_join(st));
-  if (!g.exec || g.adam_m != adam_m || g.adam_v != adam_v || g.lr != lr || g.with_auto != (int)with_auto)
-    MD2_TRY(capture_step(m, with_auto, adam_m, adam_v, lr));
+  if (!g.exec || g.adam_m != adam_m || g.adam_v != adam_v || g.lr != lr || g.with_auto != (int)with_auto ||
+      g.with_net != (int)with_net)
+    MD2_TRY(capture_step(m, with_auto, with_net, adam_m, adam_v, lr));
   const size_t xb = sizeof(float) * (size_t)m->N * 3 * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W;
   if (x != g.x) MD2_HIP(hipMemcpyAsync(g.x, x, xb, hipMemcpyDeviceToDevice, st));
+  if (with_net && x_net != g.x_net) MD2_HIP(hipMemcpyAsync(g.x_net, x_net, xb, hipMemcpyDeviceToDevice, st));
   if (with_auto)
     MD2_HIP(hipMemcpyAsync(g.autoloss, auto_loss, sizeof(float) * (size_t)m->N * m->cfg.H * m->cfg.W,
                            hipMemcpyDeviceToDevice, st));
   if (step != g.next_step) MD2_TRY(set_device_int(g.step, step - 1, st));
   MD2_HIP(hipGraphLaunch(g.exec, st));
   MD2_HIP(hipMemcpyAsync(loss, g.loss, sizeof(float), hipMemcpyDeviceToDevice, st));
-  m->cur_x = g.x;
+  m->cur_x = with_net ? g.x_net : g.x;
   m->cot_ready = 1;
   g.next_step = step + 1;
   return MD2_OK;
+}
+
+int model_train_step_graph(Model* m, const float* x, const float* auto_loss, float* adam_m,
+                           float* adam_v, float lr, int step, float* loss, hipStream_t st) {
+  return model_train_step_graph_aug(m, x, nullptr, auto_loss, adam_m, adam_v, lr, step, loss, st);
 }
 
 

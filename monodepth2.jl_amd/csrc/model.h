@@ -59,6 +59,10 @@ void model_destroy(Model* m);
 // train path
 int model_forward_loss(Model* m, const float* x, const float* automask, float* loss, float* terms,
                        hipStream_t st);
+// the same with a separate network input: the encoder (and the stem's filter gradient) reads x_net,
+// the automask and the loss tail read x; x_net == nullptr or == x is model_forward_loss
+int model_forward_loss_aug(Model* m, const float* x, const float* x_net, const float* automask, float* loss,
+                           float* terms, hipStream_t st);
 // forward only ((m)(x, source_ids, target_id), src/model.jl:31-55): outputs via model_outputs;
 // a backward after it needs model_set_cotangents
 int model_forward(Model* m, const float* x, hipStream_t st);
@@ -85,6 +89,8 @@ bool model_segment_update_enabled();
 // forward + loss + backward + ADAM(0.9, 0.999, 1e-8) replayed as one captured hipGraph
 int model_train_step_graph(Model* m, const float* x, const float* auto_loss, float* adam_m,
                            float* adam_v, float lr, int step, float* loss, hipStream_t st);
+int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, const float* auto_loss,
+                               float* adam_m, float* adam_v, float lr, int step, float* loss, hipStream_t st);
 // MPI mode: the disparity bins [N][num_bins] of the next forwards (device; copied)
 int model_set_bins(Model* m, const float* bins, hipStream_t st);
 // outputs of the last forward

@@ -16,6 +16,7 @@ from .mpi import MPIDepthDecoder, mpi_forward  # noqa: F401
 from .evaluate import METRIC_NAMES, depth_errors, evaluate_depth, garg_crop  # noqa: F401
 from .lidar import (kitti_odometry_velo_to_image, kitti_raw_velo_to_image, lidar_depth, load_velodyne,  # noqa: F401
                     post_process_disparity)
+from .color import JITTER_DTYPE, ColorJitter, color_jitter, jitter_params  # noqa: F401
 
 __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_poses", "lib", "MD2Error",
            "ADAM", "DepthDecoder", "Model", "Pose", "PoseDecoder", "ResidualNetwork", "ResNet",
@@ -26,4 +27,5 @@ __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_pos
            "MPIDepthDecoder", "mpi_forward",
            "METRIC_NAMES", "depth_errors", "evaluate_depth", "garg_crop",
            "kitti_odometry_velo_to_image", "kitti_raw_velo_to_image", "lidar_depth", "load_velodyne",
-           "post_process_disparity"]
+           "post_process_disparity",
+           "JITTER_DTYPE", "ColorJitter", "color_jitter", "jitter_params"]

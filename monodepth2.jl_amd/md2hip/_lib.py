@@ -91,6 +91,15 @@ class LidarCfg(C.Structure):
     _fields_ = [("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("forward_only", C.c_int), ("vel_depth", C.c_int)]
 
 
+JITTER_MAX_SAMPLES = 64  # include/md2.h MD2_JITTER_MAX_SAMPLES
+
+
+class Jitter(C.Structure):
+    """``md2_jitter``."""
+    _fields_ = [("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("hue", C.c_float),
+                ("order", C.c_ubyte * 4), ("apply", C.c_int)]
+
+
 _lib = None
 _load_error = None
 
@@ -172,6 +181,10 @@ _SIGS = {
     "md2_depth_eval": (C.c_int, [C.POINTER(DepthEvalCfg), P, P, P, P, P, P]),
     "md2_lidar_depth": (C.c_int, [C.POINTER(LidarCfg), P, C.POINTER(C.c_longlong), C.POINTER(C.c_float), P, P, P]),
     "md2_disp_post_process": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, P, P]),
+    "md2_color_jitter_workspace_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "md2_color_jitter": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Jitter), P, P, P, P]),
+    "md2_model_forward_loss_aug": (C.c_int, [P, P, P, P, P, P, P]),
+    "md2_model_train_step_graph_aug": (C.c_int, [P, P, P, P, P, P, C.c_float, C.c_int, P, P]),
     "md2_model_debug_tensor": (C.c_int, [P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int)]),
     "md2_model_features": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),

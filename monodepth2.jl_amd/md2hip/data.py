@@ -346,15 +346,19 @@ class DataLoader:
     host->device copy runs on a side stream while the previous batch trains.  ``bytes_h2d``
     (default): N0f8 datasets are copied as uint8 and converted on the GPU.  ``native`` (default):
     N0f8 datasets decode through the library's C++ PNG loader (md2_load_*_u8; GIL-free threads,
-    ``prefetch`` batches in flight, ``workers`` threads in all) into pinned memory."""
+    ``prefetch`` batches in flight, ``workers`` threads in all) into pinned memory.
+    ``color_jitter`` (a ``md2hip.ColorJitter``; GPU loaders only): the loader yields ``(x, x_net)``
+    instead of x -- x_net is ``color_jitter(x, color_jitter.draw(idx, seed + epoch))``, computed on
+    the side stream right after the batch arrives; x stays the un-augmented batch for the loss."""
 
     def __init__(self, dataset, batch_size: int, *, shuffle: bool = True, seed: int = 0,
                  workers: int = 8, device=None, rank: int = 0, world: int = 1, prefetch: int = 2,
-                 bytes_h2d: bool = True, native: bool = True):
+                 bytes_h2d: bool = True, native: bool = True, color_jitter=None):
         self.ds, self.batch_size, self.shuffle, self.seed = dataset, batch_size, shuffle, seed
         self.workers, self.rank, self.world, self.prefetch = workers, rank, world, prefetch
         self.bytes_h2d, self.native = bytes_h2d, native
         self.device = device
+        self.color_jitter = color_jitter
         self.epoch = 0
 
     def __len__(self):
@@ -380,6 +384,9 @@ class DataLoader:
         dev = torch.device(self.device) if self.device is not None else None
         on_gpu = dev is not None and dev.type == "cuda"
         stream = torch.cuda.Stream(device=dev) if on_gpu else None
+        jitter = self.color_jitter
+        if jitter is not None and not on_gpu:
+            raise ValueError("color_jitter runs on the GPU: the loader needs a CUDA device")
         q: "queue.Queue" = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
 
@@ -406,6 +413,7 @@ class DataLoader:
                 with ThreadPoolExecutor(jobs if native else self.workers) as pool:
                     pending = []
                     it = iter(batches)
+                    drawn = iter(batches)    # the indices of the batch being uploaded (for the jitter draw)
                     if native:               # `jobs` batches in flight, each decoded natively
                         for idx in it:
                             pending.append(pool.submit(native_batch, idx))
@@ -414,6 +422,7 @@ class DataLoader:
                     while pending or not native:
                         if stop.is_set():
                             return
+                        cur = next(drawn, None)
                         if native:
                             host = pending.pop(0).result()
                             nxt = next(it, None)
@@ -435,6 +444,8 @@ class DataLoader:
                                                                     C.c_void_p(stream.cuda_stream)),
                                           "md2_unorm8_to_float")
                                     x = xf
+                                if jitter is not None:   # the networks' input; x itself stays as loaded
+                                    x = (x, jitter(x, jitter.draw(cur, self.seed + epoch)))
                                 ev = torch.cuda.Event()
                                 ev.record(stream)
                             q.put((x, ev, host))
@@ -457,7 +468,8 @@ class DataLoader:
                 x, ev, _host = item
                 if ev is not None:
                     torch.cuda.current_stream(dev).wait_event(ev)
-                    x.record_stream(torch.cuda.current_stream(dev))
+                    for t_ in (x if isinstance(x, tuple) else (x,)):
+                        t_.record_stream(torch.cuda.current_stream(dev))
                 yield x
         finally:
             stop.set()

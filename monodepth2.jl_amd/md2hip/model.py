@@ -247,14 +247,27 @@ class _Executor:
               "md2_model_set_disparity_bins")
         self._bins = b                       # the copy is async: keep the source alive
 
-    def forward_loss(self, x, auto_loss=None, loss=None, terms=None):
+    def _check_net(self, x, x_net):
+        import torch
+        if (tuple(x_net.shape) != tuple(x.shape) or x_net.dtype != torch.float32 or x_net.device != x.device
+                or not x_net.is_contiguous()):
+            raise ValueError("x_net must be a contiguous float32 tensor shaped and placed like x")
+
+    def forward_loss(self, x, auto_loss=None, loss=None, terms=None, x_net=None):
+        """``x_net`` (like x, e.g. ``color_jitter(x, ...)``): the frames the networks see; the automask
+        and the loss tail read x (md2_model_forward_loss_aug).  None: the plain call."""
         import torch
         self.model._require_train("train_loss / forward_loss")
         loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=x.device)
         self.sync()
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
-        check(lib().md2_model_forward_loss(self.handle, ptr(x), ptr(am), ptr(loss), ptr(terms),
-                                           stream_of(x.device)), "md2_model_forward_loss")
+        if x_net is None:
+            check(lib().md2_model_forward_loss(self.handle, ptr(x), ptr(am), ptr(loss), ptr(terms),
+                                               stream_of(x.device)), "md2_model_forward_loss")
+        else:
+            self._check_net(x, x_net)
+            check(lib().md2_model_forward_loss_aug(self.handle, ptr(x), ptr(x_net), ptr(am), ptr(loss), ptr(terms),
+                                                   stream_of(x.device)), "md2_model_forward_loss_aug")
         self.forwarded = self.pending = True
         self._trained()
         return loss
@@ -289,10 +302,12 @@ class _Executor:
         self._cot_keep = (keep, dp)           # the copies are async: keep the sources alive
         self.cotangents = True
 
-    def train_step_graph(self, x, opt: "ADAM", auto_loss=None, loss=None):
+    def train_step_graph(self, x, opt: "ADAM", auto_loss=None, loss=None, x_net=None):
         """One full step (forward, loss, backward, Flux ADAM with opt's state) replayed as a
         captured hipGraph (md2_model_train_step_graph): the same kernels in the same order as
-        forward_loss + backward + ADAM.update, without per-launch host work.  Returns the loss."""
+        forward_loss + backward + ADAM.update, without per-launch host work.  Returns the loss.
+        ``x_net`` as for ``forward_loss`` (md2_model_train_step_graph_aug; the step is captured again
+        when its presence changes)."""
         import torch
         self.model._require_train("train_step_graph")
         if tuple(opt.beta) != (0.9, 0.999) or opt.eps != 1e-8:
@@ -304,9 +319,15 @@ class _Executor:
             opt.v = torch.zeros_like(self.model.flat)
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
         opt.t += 1
-        check(lib().md2_model_train_step_graph(self.handle, ptr(x), ptr(am), ptr(opt.m), ptr(opt.v), opt.eta,
-                                               opt.t, ptr(loss), stream_of(x.device)),
-              "md2_model_train_step_graph")
+        if x_net is None:
+            check(lib().md2_model_train_step_graph(self.handle, ptr(x), ptr(am), ptr(opt.m), ptr(opt.v), opt.eta,
+                                                   opt.t, ptr(loss), stream_of(x.device)),
+                  "md2_model_train_step_graph")
+        else:
+            self._check_net(x, x_net)
+            check(lib().md2_model_train_step_graph_aug(self.handle, ptr(x), ptr(x_net), ptr(am), ptr(opt.m),
+                                                       ptr(opt.v), opt.eta, opt.t, ptr(loss), stream_of(x.device)),
+                  "md2_model_train_step_graph_aug")
         self.forwarded = True
         self._trained()
         self.model._last = self
@@ -537,17 +558,18 @@ def disparity_bins(batch: int, num_bins: int, u=None, device="cuda", near=1.0, f
 
 
 def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
-               do_visualization: bool = False, num_bins: int = 32, bins=None):
+               do_visualization: bool = False, num_bins: int = 32, bins=None, x_net=None):
     """``train_loss(model, x, auto_loss, cache, params, do_visualization)`` (src/training.jl:21).
     Runs the forward and the fused loss-tail pullback; call ``gradient(model)`` for the rest of
     the backward.  Returns (loss, vis_disparity, vis_warped, vis_loss).  MPI mode (the model's
     DepthDecoder has embedding_levels > 0; batch 1): ``num_bins`` planes, ``bins`` [1, num_bins]
-    (default: a fresh draw of md2hip.disparity_bins)."""
+    (default: a fresh draw of md2hip.disparity_bins).  ``x_net`` (like x; not in MPI mode): the
+    colour-augmented frames the networks see, while the loss, SSIM and the automask stay on x."""
     model._require_train("train_loss")
     ex = model.executor(tuple(x.shape), cache, params, num_bins)
     if ex.emb:
         ex.set_bins(disparity_bins(x.shape[0], num_bins, device=x.device) if bins is None else bins)
-    loss = ex.forward_loss(x, auto_loss)
+    loss = ex.forward_loss(x, auto_loss, x_net=x_net)
     if not do_visualization:
         return loss, None, None, None
     # training.jl:34-37,71-74: the last disparity, both warped sources and the per-pixel warp
@@ -681,10 +703,11 @@ class ADAM:
         ex.version = model.version
 
 
-def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, opt: ADAM):
-    """One ``gradient(θ) do train_loss(...)[1] end`` + ``update!`` on one GPU."""
+def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, opt: ADAM, x_net=None):
+    """One ``gradient(θ) do train_loss(...)[1] end`` + ``update!`` on one GPU (``x_net``: see
+    ``train_loss``)."""
     model._require_train("train_step")
-    loss, *_ = train_loss(model, x, auto_loss, cache, params)
+    loss, *_ = train_loss(model, x, auto_loss, cache, params, x_net=x_net)
     gradient(model)
     opt.update(model)
     return loss
