@@ -1,6 +1,6 @@
 """GPU: the launch-boundary split-K reduce (a split-K conv's slabs summed by the BatchNorm
-statistics pass / the BN-backward partial pass, conv_f_bn / conv_d_bn in model.cpp) and the float4
-split-K reduction change no bit of the train step: parameters, ADAM moments and losses after
+statistics pass / the BN-backward partial pass, conv_f_bn in model_forward.cpp / conv_d_bn in
+model_backward.cpp) and the float4 split-K reduction change no bit of the train step: parameters, ADAM moments and losses after
 several steps at the benchmarked configuration (B=12, 416x128: layer3/layer4 convs run split-K)
 equal those of the separate-reduction path (MD2_FUSE_SPLITK=0).  Likewise the fused stem passes:
 BN + ReLU + max pool in one forward kernel (MD2_FUSE_POOL_FWD), the stem's decoder skip gradient
