@@ -691,6 +691,84 @@ int md2_model_train_step_graph_aug(md2_model* m, const float* x, const float* x_
                                    const float* auto_loss, float* adam_m, float* adam_v,
                                    float lr, int step, float* loss, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Odometry evaluation: the poses of consecutive frames without the DepthDecoder, and Monodepth2's
+ * KITTI odometry metric -- the scale-aligned absolute trajectory error (ATE) over snippets of
+ * track_length frames -- entirely on the device.  Additive: MD2_ABI_VERSION is unchanged.
+ *
+ * md2_model_eval_pose
+ * x [n][c][h][w], 2 <= n <= 2*batch + 1: encoder on the n frames, PoseDecoder on the n-1 pairs
+ * (frame i, frame i+1).  *pose -> [n-1][6] = (rvec, tvec) of pair i, the RAW network output,
+ * i.e. what md2_model_forward writes for that pair before composeT / inversion.
+ * Buffer reuse and the MD2_ESTATE rules are those of md2_model_eval_disparity.
+ * The executor's buffers hold 3*batch images and 2*batch pairs, hence the limit (MD2_EINVAL outside
+ * it); BatchNorm as md2_model_eval_disparity (running statistics in test mode, else the statistics
+ * of the n frames, which then move the running ones); MPI mode (embedding_levels > 0): MD2_ENOTSUP.
+ *
+ * md2_pose_eval
+ * pred [M][6]: raw (rvec, tvec) steps, step k relating frame k and frame k+1 of its sequence;
+ * gt_rel [M][12]: ground-truth steps (R row-major, t) in fp32; offsets [nseq+1]: a HOST array, read
+ * before the call returns, offsets[0] = 0, sequence s = steps offsets[s] .. offsets[s+1]-1 and
+ * M = offsets[nseq].  The ground truth is relative because global KITTI translations reach hundreds
+ * of metres: differencing them in fp32 costs millimetres against ATEs of about a centimetre, so the
+ * host forms D_k = inv(G_k) G_{k+1} in fp64 and rounds once.
+ *  1. Step transforms.  D_k = composeT(so3_exp_map(rvec_k), tvec_k, invert): the kernel of
+ *     md2_so3_compose_fwd itself (R = I + f1 S + f2 S^2 with S = hat(rvec), theta = |rvec|,
+ *     f1 = sin(theta) / max(theta, 1e-4), f2 = (1 - cos(theta)) / max(theta, 1e-4)^2, evaluated in
+ *     fp64 and rounded once to fp32); invert = 1 gives (R^T, R^T (-t)).  The network's output for the
+ *     pair (k, k+1) maps camera-k points into camera k+1; the chain below wants the pose of camera
+ *     k+1 in camera k's frame, so a caller scoring md2_model_eval_pose passes invert = 1 with a
+ *     gt_rel of that convention (D_k = inv(G_k) G_{k+1} for camera-to-world G).  Monodepth2's own
+ *     evaluate_pose.py chains the un-inverted output; invert = 0 reproduces it.  rt_out [M][12]
+ *     (NULL: not wanted) receives D_k.
+ *  2. Snippets.  With L = track_length, a sequence of m steps has S = m - L + 2 snippets (0 when
+ *     m < L - 1); snippet i uses steps i .. i+L-2 of its sequence and never crosses a boundary.
+ *     C_0 = I, C_{j+1} = C_j o D_{i+j} with (R,t) o (R',t') = (R R', R t' + t); every entry is
+ *     rounded in fp32 on its own, in this order: (a0*b0 + a1*b1) + a2*b2, then + t for the
+ *     translation.  p_j = the translation of C_j, j = 0..L-1 (p_0 = 0: both chains start at the
+ *     origin, so Monodepth2's first-frame offset is zero); q_j likewise from gt_rel.
+ *  3. Per snippet, out [S_total][3] = (ate, scale, rot_chord), the snippets of sequence 0 first,
+ *     in order.  In fp32, starting from 0 and added one term after the other over j = 1..L-1 then
+ *     the component 0..2 (p_0 = q_0 = 0 contribute nothing):  num = sum q*p, den = sum p*p;  scale = den > 0 ? num / den : 0  (Monodepth2 divides regardless
+ *     and reports NaN for a motionless prediction; here its ATE is that of the zero trajectory);
+ *     ate = sqrtf(sum (p*scale - q)^2) / (float)L  -- Monodepth2's compute_ate: the root of the sum,
+ *     divided by the number of frames;  rot_chord = sqrtf(sum over the nine entries, row-major, of
+ *     (Rp - Rq)^2) for the rotations of C_{L-1}: the Frobenius distance, 2 sqrt(2) sin(angle / 2)
+ *     of the relative rotation.  Division and square roots are correctly rounded; there is no
+ *     inverse trigonometry on the device (callers convert the chord to an angle).
+ *  4. Per sequence, over the snippets whose three values are all finite (the others are counted in
+ *     n_bad): summary [nseq][4] = (mean_ate, std_ate, mean_scale, mean_rot_chord), std_ate the
+ *     population deviation (as np.std), two-pass; counts [nseq][2] = (snippets S, n_bad).  A sequence
+ *     without a finite snippet gives four NaNs.  The sums are fp64 in a fixed order: one block of 256
+ *     threads per sequence; thread t adds the values of snippets t, t + 256, ... ascending (a
+ *     skipped snippet adds nothing); the 64 lanes of a wave are combined by a butterfly (partner
+ *     lane ^ 32, 16, 8, 4, 2, 1), the four waves as (w0 + w1) + (w2 + w3).  mean = sum / count in
+ *     fp64; the second pass sums (ate - mean)^2 the same way, std = sqrt(sum / count); each result is
+ *     rounded to fp32 once.
+ * Three launches on `stream` (steps, snippets: one thread each; sequences: one block each), no
+ * allocation, no host synchronisation, no atomics: BITWISE REPRODUCIBLE.  offsets ride in the
+ * kernels' argument block (the reason for the MD2_POSE_EVAL_MAX_SEQ cap; callers chunk longer
+ * lists).  The workspace (md2_pose_eval_workspace_size(M) bytes of device memory, 0 for M outside
+ * 0..2^24; any content) is written before it is read.
+ * MD2_EINVAL (checked before any HIP call): a null offsets, summary, counts or workspace; null pred
+ * or gt_rel unless M == 0; null out unless there is no snippet; nseq outside
+ * 1..MD2_POSE_EVAL_MAX_SEQ; track_length outside 2..MD2_POSE_EVAL_MAX_TRACK; invert not 0 or 1;
+ * offsets[0] != 0, a decreasing offset or M > 2^24.
+ * ---------------------------------------------------------------------------------------- */
+#define MD2_POSE_EVAL_MAX_SEQ 64
+#define MD2_POSE_EVAL_MAX_TRACK 16
+int md2_model_eval_pose(md2_model* m, const float* x, int n, const float** pose, void* stream);
+size_t md2_pose_eval_workspace_size(long long m);
+int md2_pose_eval(const float* pred,            /* device [M][6]                                  */
+                  const float* gt_rel,          /* device [M][12]                                 */
+                  const long long* offsets,     /* HOST [nseq+1]                                  */
+                  int nseq, int track_length, int invert,
+                  float* out,                   /* device [S_total][3] = ate, scale, rot_chord    */
+                  float* summary,               /* device [nseq][4]                               */
+                  int* counts,                  /* device [nseq][2] = snippets, n_bad             */
+                  float* rt_out,                /* device [M][12] or NULL                         */
+                  void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -526,6 +526,17 @@ function eval_disparity(m::HIPModel, x::ROCArray{Float32,4})
             for k in 1:m.cfg.n_levels]
 end
 
+# eval_pose(m, x) -- the PoseDecoder on the consecutive frames of x::(W,H,C,n), 2 <= n <= 2*batch+1,
+# without the DepthDecoder: (6, n-1), column i = the raw (rvec, tvec) of the pair (frame i, frame i+1).
+# Wraps an executor-owned buffer that the model's next forward overwrites: copy to keep.
+function eval_pose(m::HIPModel, x::ROCArray{Float32,4})
+    p = Ref{Ptr{Float32}}(C_NULL)
+    check(ccall((:md2_model_eval_pose, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Cint, Ptr{Ptr{Float32}}, Ptr{Cvoid}),
+                m.handle, x, size(x, 4), p, stream_ptr()))
+    return unsafe_wrap(ROCArray, p[], (6, size(x, 4) - 1))
+end
+
 # ------------------------------------------------------------------------------------------------
 # Op-level forward + rrule pairs (src/utils.jl, src/training.jl): for callers that keep Flux for
 # the networks and differentiate the loss ops one at a time.
@@ -785,6 +796,34 @@ function color_jitter(x::ROCArray{Float32,5}, params::Vector{Jitter}; out=simila
                  Ptr{Cvoid}),
                 x, n, frames, c, h, w, params, out, means, ws, stream_ptr()))
     return return_means ? (out, means) : out
+end
+
+# Odometry evaluation (Monodepth2's snippet ATE; include/md2.h states every operation): pred (6, M)
+# raw (rvec, tvec) steps, gt_rel (12, M) ground-truth steps (R row-major, t), offsets: nseq+1 0-based
+# host offsets from 0 to M splitting the steps into sequences.  Returns device arrays per_snippet
+# (3, S) = ate, scale, rot_chord, summary (4, nseq) = mean_ate, std_ate, mean_scale, mean_rot_chord
+# and counts (2, nseq) = snippets, n_bad; with return_rt also the step transforms (12, M).
+# invert=true inverts every predicted step first (eval_pose outputs against inv(G_k) G_{k+1}).
+# At most POSE_EVAL_MAX_SEQ sequences per call.  No host sync.
+const POSE_EVAL_MAX_SEQ = 64
+function pose_errors(pred::ROCArray{Float32,2}, gt_rel::ROCArray{Float32,2};
+                     offsets::Vector{Int64}=Int64[0, size(pred, 2)], track_length=5, invert=true, return_rt=false)
+    size(pred, 1) == 6 || error("pred must be (6, M)")
+    M = size(pred, 2)
+    size(gt_rel) == (12, M) || error("gt_rel must be (12, ", M, ")")
+    nseq = length(offsets) - 1
+    1 <= nseq <= POSE_EVAL_MAX_SEQ || error("1..", POSE_EVAL_MAX_SEQ, " sequences per call, got ", nseq)
+    (offsets[1] == 0 && offsets[end] == M) || error("offsets must run from 0 to the number of steps")
+    S = sum(max(offsets[i + 1] - offsets[i] - track_length + 2, 0) for i in 1:nseq)
+    out = ROCArray{Float32}(undef, 3, S); summary = ROCArray{Float32}(undef, 4, nseq)
+    counts = ROCArray{Int32}(undef, 2, nseq); rt = ROCArray{Float32}(undef, 12, M)
+    ws = ROCVector{UInt8}(undef, max(ccall((:md2_pose_eval_workspace_size, lib), Csize_t, (Clonglong,), M), 256))
+    check(ccall((:md2_pose_eval, lib), Cint,
+                (Ptr{Float32}, Ptr{Float32}, Ptr{Clonglong}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32},
+                 Ptr{Int32}, Ptr{Float32}, Ptr{UInt8}, Ptr{Cvoid}),
+                pred, gt_rel, offsets, nseq, track_length, invert ? 1 : 0, out, summary, counts, rt, ws,
+                stream_ptr()))
+    return return_rt ? (out, summary, counts, rt) : (out, summary, counts)
 end
 
 function find_static(dataset, α; batch=16)

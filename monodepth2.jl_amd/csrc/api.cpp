@@ -612,6 +612,11 @@ int md2_model_eval_disparity(md2_model* m, const float* x, int n, const float** 
   return MD2_OK;
 }
 
+int md2_model_eval_pose(md2_model* m, const float* x, int n, const float** pose, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_eval_pose(m->impl, x, n, pose, (hipStream_t)stream);
+}
+
 int md2_arch_bn_stat_count(const md2_model_cfg* cfg, long long* n_bn, long long* n_elems) {
   MD2_CHECK_ARG(cfg != nullptr, "cfg");
   MD2_CHECK_ARG(cfg->embedding_levels >= 0, "embedding_levels >= 0");

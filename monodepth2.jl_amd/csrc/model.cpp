@@ -394,6 +394,21 @@ int model_eval_disparity(Model* m, const float* x, int n, float** disp_out, hipS
   return MD2_OK;
 }
 
+int model_eval_pose(Model* m, const float* x, int n, const float** pose_out, hipStream_t st) {
+  MD2_CHECK_ARG(m && x, "eval_pose: model/x");
+  MD2_CHECK_ARG(n >= 2 && n - 1 <= 2 * m->N, "eval_pose: 2 <= n <= 2 * batch + 1");
+  MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
+  if (m->E > 0) {
+    set_error("eval_pose: not available in MPI mode (embedding_levels > 0)");
+    return MD2_ENOTSUP;
+  }
+  // as eval_disparity: the executor's activation buffers are reused, a pending train forward is gone
+  m->cur_x = nullptr;
+  MD2_TRY(m->eval_pose(Model::tin(x, m->cfg.arch.in_ch, (long)m->cfg.H * m->cfg.W), n, st));
+  if (pose_out) *pose_out = m->pose;
+  return MD2_OK;
+}
+
 // Flux-layout flat vectors (src/model.jl @functor order, conv weights as true convolutions) <->
 // the library's flat vectors: a copy with every conv weight's taps reversed (md2_model_*_params)
 static int flux_flip_copy(const Model* m, const float* src, float* dst, hipStream_t st) {

@@ -99,6 +99,9 @@ int model_outputs(Model* m, const float** disp, int* dw, int* dh, const float** 
 int model_features(Model* m, const float** feat, int* c, int* h, int* w);
 // inference: eval_disparity (src/model.jl:63) on x [n][C][H][W], n <= N*3
 int model_eval_disparity(Model* m, const float* x, int n, float** disp_out, hipStream_t st);
+// inference: the PoseDecoder on the n-1 pairs (frame i, frame i+1) of x [n][C][H][W], 2 <= n <= 2N+1;
+// no DepthDecoder.  *pose_out -> [n-1][6] raw (rvec, tvec)
+int model_eval_pose(Model* m, const float* x, int n, const float** pose_out, hipStream_t st);
 int model_debug_tensor(Model* m, int index, const char** name, const void** ptr, int* dims);
 long model_param_count(Model* m);
 // flat vectors in Flux layout (conv weights as true convolutions: taps reversed)

@@ -289,6 +289,23 @@ int Model::pose_fwd(hipStream_t st) {
   return pose_head_fwd(pc2, 2 * N, 256, hw4, P(spec.p3.w), P(spec.p3.b), means, pose, st);
 }
 
+// Pose-only inference on n consecutive frames (images 0..n-1 of `in`): the encoder, the squeezer on
+// the n images, then the PoseDecoder on the n-1 pairs (i, i+1).  Consecutive pairs need no gather:
+// the second half of pair i is image i+1, one image stride further into sqo (pose_pairs_in's trick
+// with a shift of 1 instead of N).  Fits the buffers for n <= 2N+1 (<= 3N images, <= 2N pairs).
+int Model::eval_pose(const TensorIn& in, int n, hipStream_t st) {
+  MD2_TRY(encoder(in, n, st));
+  SideScratch side(ov);   // the pose convs' workspace is the side one (pose_fwd)
+  const long hw4 = (long)featH[4] * featW[4];
+  MD2_TRY(conv_f(sq, n, tin(feat[4], featC[4], hw4), sqo, 256 * hw4, ACT_RELU, st));
+  TensorIn pairs = tin(sqo, 256, hw4);
+  pairs.p1 = sqo + 256 * hw4;
+  pairs.bs1 = 256 * hw4;
+  MD2_TRY(conv_f(p1, n - 1, pairs, pc1, 256 * hw4, ACT_RELU, st));
+  MD2_TRY(conv_f(p2, n - 1, tin(pc1, 256, hw4), pc2, 256 * hw4, ACT_RELU, st));
+  return pose_head_fwd(pc2, n - 1, 256, hw4, P(spec.p3.w), P(spec.p3.b), means, pose, st);
+}
+
 // (m)(x, source_ids, target_id) (src/model.jl:31-55): encoder on the 3N frames, DepthDecoder on
 // the targets, PoseDecoder on the pairs -- disparities and poses, no loss tail
 int Model::forward(const float* x, hipStream_t st) {

@@ -350,6 +350,7 @@ class Model {
   int mpi_embed(int nimg, int img0, hipStream_t st);
   int decoder_fwd(int nimg, int img0, hipStream_t st);
   int pose_fwd(hipStream_t st);
+  int eval_pose(const TensorIn& in, int n, hipStream_t st);
   int forward(const float* x, hipStream_t st);
   int forward_loss(const float* x, const float* x_net, const float* automask, float* loss, float* terms,
                    hipStream_t st);

@@ -100,6 +100,9 @@ class Jitter(C.Structure):
                 ("order", C.c_ubyte * 4), ("apply", C.c_int)]
 
 
+POSE_EVAL_MAX_SEQ = 64   # include/md2.h MD2_POSE_EVAL_MAX_SEQ
+POSE_EVAL_MAX_TRACK = 16  # include/md2.h MD2_POSE_EVAL_MAX_TRACK
+
 _lib = None
 _load_error = None
 
@@ -185,6 +188,9 @@ _SIGS = {
     "md2_color_jitter": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Jitter), P, P, P, P]),
     "md2_model_forward_loss_aug": (C.c_int, [P, P, P, P, P, P, P]),
     "md2_model_train_step_graph_aug": (C.c_int, [P, P, P, P, P, P, C.c_float, C.c_int, P, P]),
+    "md2_model_eval_pose": (C.c_int, [P, P, C.c_int, C.POINTER(C.c_void_p), P]),
+    "md2_pose_eval_workspace_size": (C.c_size_t, [C.c_longlong]),
+    "md2_pose_eval": (C.c_int, [P, P, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, P, P, P, P, P, P]),
     "md2_model_debug_tensor": (C.c_int, [P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int)]),
     "md2_model_features": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),

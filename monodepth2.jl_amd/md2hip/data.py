@@ -481,6 +481,37 @@ class DataLoader:
             t.join()
 
 
+def load_kitti_poses(path):
+    """A KITTI odometry ``poses/XX.txt`` file -- one camera-to-world pose per frame, 12 values per
+    line, the row-major 3x4 ``[R | t]`` -- as float64 ``[F, 3, 4]``."""
+    rows = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            v = line.split()
+            if not v:
+                continue
+            if len(v) != 12:
+                raise ValueError(f"{path}:{no}: {len(v)} values, a pose line holds 12")
+            rows.append([float(s) for s in v])
+    return np.array(rows, dtype=np.float64).reshape(-1, 3, 4)
+
+
+def relative_poses(G):
+    """The steps between consecutive global poses ``G [F, 3, 4]`` (camera-to-world, as
+    ``load_kitti_poses`` returns them): float32 ``[F-1, 12]``, row k = ``inv(G_k) @ G_{k+1}`` as
+    (R row-major, t) -- the pose of camera k+1 in camera k's frame, the ``gt_rel`` of
+    ``md2hip.pose_errors``.  Composed in float64 and rounded once: global translations reach
+    hundreds of metres, and differencing them in float32 would cost millimetres."""
+    G = np.asarray(G, dtype=np.float64)
+    if G.ndim != 3 or G.shape[1:] != (3, 4) or G.shape[0] < 1:
+        raise ValueError("G must be [F, 3, 4] with F >= 1")
+    R, t = G[:, :, :3], G[:, :, 3]
+    Rt = np.transpose(R[:-1], (0, 2, 1))                        # inv of a rigid pose: (R^T, -R^T t)
+    dR = Rt @ R[1:]
+    dt = np.einsum("kij,kj->ki", Rt, t[1:] - t[:-1])
+    return np.concatenate([dR.reshape(-1, 9), dt], axis=1).astype(np.float32)
+
+
 def find_static(dataset, alpha: float, batch: int = 16, device=None, seed: int = 0) -> List[str]:
     """``find_static(dataset, α)`` (src/dtk.jl:51-69): the files of the samples whose mean
     identity-reprojection loss (``automasking_loss`` of the raw frames against the target) exceeds

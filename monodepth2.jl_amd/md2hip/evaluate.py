@@ -3,7 +3,12 @@ the seven error metrics) over the C-ABI (``md2_depth_eval``, include/md2.h).  No
 
 ``depth_errors`` scores one batch of disparities against ground-truth depth in one batched call
 and returns device tensors without a sync; ``evaluate_depth`` runs a model over a dataset's
-batches, accumulates on the device and syncs once."""
+batches, accumulates on the device and syncs once.
+
+Odometry evaluation (``md2_pose_eval``): ``pose_errors`` scores predicted pose steps against
+ground-truth steps over 5-frame snippets (scale-aligned absolute trajectory error and a rotation
+error) without a sync; ``evaluate_pose`` runs ``eval_pose`` over a sequence's windows and syncs
+once."""
 from __future__ import annotations
 
 import ctypes as C
@@ -74,6 +79,149 @@ def depth_errors(disp, gt, *, crop="garg", min_depth=0.1, max_depth=100.0, eval_
         check(lib().md2_depth_eval(C.byref(cfg), ptr(disp), ptr(gt), ptr(metrics), ptr(counts), ptr(ws),
                                    stream_of(disp.device)), "md2_depth_eval")
     return metrics, counts
+
+
+def _snippet_counts(offsets, track_length):
+    return np.maximum(np.diff(offsets) - track_length + 2, 0)
+
+
+def pose_errors(pred, gt_rel, offsets=None, track_length=5, invert=True, *, rt_out=None):
+    """Monodepth2's odometry metric of predicted steps ``pred [M, 6]`` (raw ``(rvec, tvec)`` rows,
+    e.g. ``eval_pose`` outputs concatenated) against ground-truth steps ``gt_rel [M, 12]``
+    (``md2hip.data.relative_poses``), both float32 on the GPU (``md2_pose_eval``; include/md2.h
+    states every operation).
+
+    ``offsets`` (``nseq + 1`` host integers from 0 to M; default: one sequence) splits the steps
+    into sequences.  Every run of ``track_length - 1`` consecutive steps of a sequence is a snippet
+    of ``track_length`` frames: both trajectories are chained from the identity, the prediction is
+    scaled onto the ground truth by least squares, and the snippet's ``ate`` is the root of the
+    summed squared position error divided by the number of frames (Monodepth2's ``compute_ate``).
+    ``invert=True`` inverts every predicted step first -- the network's pair output maps camera-k
+    points into camera k+1, the chain wants the pose of camera k+1 in camera k's frame;
+    ``invert=False`` chains the raw output as Monodepth2's evaluate_pose.py does.
+
+    Returns ``(per_snippet [S, 3] = (ate, scale, rot_chord), summary [nseq, 4] = (mean_ate, std_ate,
+    mean_scale, mean_rot_chord), counts [nseq, 2] int32 = (snippets, n_bad))`` on the device.
+    ``rot_chord`` is the Frobenius distance of the final rotations, ``2 sqrt(2) sin(angle / 2)``
+    (``chord_to_degrees``); a snippet with a non-finite value counts in ``n_bad`` and is left out of
+    the summary, a sequence without a finite snippet gives NaNs.  ``rt_out`` (``[M, 12]`` float32,
+    optional) receives the predicted step transforms.  Bitwise reproducible; enqueues on the current
+    stream and does not synchronise.  More than 64 sequences go through in chunks of 64."""
+    import torch
+    from ._lib import POSE_EVAL_MAX_SEQ, POSE_EVAL_MAX_TRACK
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt_rel, torch.Tensor):
+        raise ValueError("pred and gt_rel must be torch tensors")
+    _check_f32_cuda(pred, "pred")
+    _check_f32_cuda(gt_rel, "gt_rel")
+    if pred.dim() != 2 or pred.shape[1] != 6:
+        raise ValueError("pred must be [M, 6]")
+    M = int(pred.shape[0])
+    if tuple(gt_rel.shape) != (M, 12):
+        raise ValueError(f"gt_rel must be [{M}, 12] for {M} predicted steps")
+    if pred.device != gt_rel.device:
+        raise ValueError("pred and gt_rel must be on the same device")
+    L = int(track_length)
+    if not 2 <= L <= POSE_EVAL_MAX_TRACK:
+        raise ValueError(f"track_length must be in 2..{POSE_EVAL_MAX_TRACK}")
+    if offsets is None:
+        offsets = [0, M]
+    offsets = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets)
+    if offsets.ndim != 1 or offsets.size < 2 or offsets.dtype.kind not in "iu":
+        raise ValueError("offsets must be a 1-D integer sequence of nseq + 1 entries")
+    offsets = offsets.astype(np.int64)
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] != M:
+        raise ValueError("offsets must start at 0, not decrease and end at the number of steps")
+    if rt_out is not None:
+        _check_f32_cuda(rt_out, "rt_out")
+        if tuple(rt_out.shape) != (M, 12) or rt_out.device != pred.device:
+            raise ValueError(f"rt_out must be [{M}, 12] on pred's device")
+    nseq = int(offsets.size) - 1
+    snips = _snippet_counts(offsets, L)
+    soff = np.concatenate([[0], np.cumsum(snips)]).astype(np.int64)
+    dev = pred.device
+
+    def at(t, row):          # pointer to a row of a contiguous 2-D tensor (NULL for an empty one)
+        return C.c_void_p(t.data_ptr() + row * t.stride(0) * t.element_size()) if t.numel() else None
+    with torch.cuda.device(dev):
+        out = torch.empty(int(soff[-1]), 3, dtype=torch.float32, device=dev)
+        summary = torch.empty(nseq, 4, dtype=torch.float32, device=dev)
+        counts = torch.empty(nseq, 2, dtype=torch.int32, device=dev)
+        longest = max(int(offsets[min(nseq, a + POSE_EVAL_MAX_SEQ)] - offsets[a])
+                      for a in range(0, nseq, POSE_EVAL_MAX_SEQ))
+        ws = torch.empty(max(int(lib().md2_pose_eval_workspace_size(longest)), 256), dtype=torch.uint8, device=dev)
+        for a in range(0, nseq, POSE_EVAL_MAX_SEQ):
+            b = min(nseq, a + POSE_EVAL_MAX_SEQ)
+            base = int(offsets[a])                  # the library wants offsets[0] == 0: rebase the chunk
+            off = (C.c_longlong * (b - a + 1))(*(int(o) - base for o in offsets[a:b + 1]))
+            check(lib().md2_pose_eval(at(pred, base), at(gt_rel, base), off, b - a, L, 1 if invert else 0,
+                                      at(out, int(soff[a])), ptr(summary[a:b]), ptr(counts[a:b]),
+                                      None if rt_out is None else at(rt_out, base), ptr(ws), stream_of(dev)),
+                  "md2_pose_eval")
+    return out, summary, counts
+
+
+def chord_to_degrees(chord):
+    """The rotation angle in degrees of a ``rot_chord`` (NumPy, host): ``chord = 2 sqrt(2)
+    sin(angle / 2)``, clipped at the largest possible chord."""
+    c = np.clip(np.asarray(chord, dtype=np.float64) / (2.0 * np.sqrt(2.0)), 0.0, 1.0)
+    return np.degrees(2.0 * np.arcsin(c))
+
+
+def pose_windows(x_seq, max_pairs):
+    """The frames ``x_seq [F, C, H, W]`` of one sequence cut into windows of at most ``max_pairs + 1``
+    frames that overlap by one frame, so that the windows' pairs are the sequence's F - 1 consecutive
+    pairs, each once: what ``evaluate_pose`` takes as ``frames``.  ``max_pairs`` is twice the batch
+    of the executor that will run them (``eval_pose`` accepts 2 * batch + 1 frames).  Views of
+    ``x_seq``, made contiguous where they are not."""
+    F = int(x_seq.shape[0])
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError("max_pairs must be at least 1")
+    if F < 2:
+        raise ValueError("a sequence needs at least two frames")
+    return [x_seq[a:min(F, a + max_pairs + 1)].contiguous() for a in range(0, F - 1, max_pairs)]
+
+
+def evaluate_pose(model, frames, gt_rel, *, track_length=5, allow_nonfinite=False):
+    """Score ``model``'s PoseDecoder over one sequence: ``frames`` is an iterable of ``[n, C, H, W]``
+    device windows that overlap by one frame (the last frame of a window is the first of the next;
+    the caller builds them, ``pose_windows(x_seq, max_pairs)`` does it for frames already on the
+    device), ``gt_rel [M, 12]`` the ground-truth steps of the M pairs the windows cover together
+    (``md2hip.data.relative_poses(load_kitti_poses(...))``; NumPy or a tensor).  Each window runs
+    through ``eval_pose`` in whatever mode the model is in -- call ``model.testmode()`` first, so that
+    BatchNorm uses its running statistics and a pair's pose does not depend on its window -- the
+    outputs are concatenated on the device and scored by ``pose_errors(..., invert=True)``; the host
+    syncs once at the end.
+
+    Returns a dict: ``ate_mean``, ``ate_std`` (over the finite snippets), ``rot_deg_mean`` (the
+    mean rotation chord as an angle, degrees), ``scale_mean``, ``snippets``, ``n_bad`` (snippets
+    with a non-finite value) and ``nonfinite_inputs`` (elements of the frames that are NaN or
+    infinite: checked because the network's ReLUs turn a NaN into 0).  ``n_bad > 0`` or
+    ``nonfinite_inputs > 0`` raises ``RuntimeError`` unless ``allow_nonfinite``."""
+    import torch
+    from .model import eval_pose
+    poses, bad_in = [], None
+    for x in frames:
+        nf = (~torch.isfinite(x)).sum()                     # stays on the device
+        bad_in = nf if bad_in is None else bad_in + nf
+        poses.append(eval_pose(model, x))
+    if not poses:
+        raise ValueError("evaluate_pose: no frames")
+    pred = torch.cat(poses)
+    gt = torch.as_tensor(gt_rel).to(device=pred.device, dtype=torch.float32).contiguous()
+    if tuple(gt.shape) != (pred.shape[0], 12):
+        raise ValueError(f"gt_rel must be [{pred.shape[0]}, 12] for the {pred.shape[0]} pairs of the windows, "
+                         f"got {list(gt.shape)}")
+    _, summary, counts = pose_errors(pred, gt, track_length=track_length, invert=True)
+    s = summary.cpu().numpy().astype(np.float64)[0]         # the one sync
+    c = counts.cpu().numpy()[0]
+    bad_in = int(bad_in.cpu())
+    n_bad = int(c[1])
+    if (n_bad or bad_in) and not allow_nonfinite:
+        raise RuntimeError(f"evaluate_pose: {n_bad} snippets have a non-finite error, {bad_in} input elements "
+                           "are not finite (pass allow_nonfinite=True to score regardless)")
+    return {"ate_mean": float(s[0]), "ate_std": float(s[1]), "rot_deg_mean": float(chord_to_degrees(s[3])),
+            "scale_mean": float(s[2]), "snippets": int(c[0]), "n_bad": n_bad, "nonfinite_inputs": bad_in}
 
 
 def evaluate_depth(model, batches, *, allow_nonfinite=False, post_process=False, **depth_errors_kwargs):

@@ -740,3 +740,33 @@ def eval_disparity(model: Model, x, cache: Optional[TrainCache] = None):
         f = 2 ** (5 - l)
         shapes.append((N, 1, H // f, W // f))
     return [_wrap(dptr[i], shapes[i], x.device) for i in range(nl)]
+
+
+def eval_pose(model: Model, x):
+    """The PoseDecoder on the consecutive frames of x [n, C, H, W], n >= 2, without the DepthDecoder
+    (``md2_model_eval_pose``): an ``[n-1, 6]`` tensor whose row i is the raw network output
+    (rvec, tvec) for the pair (frame i, frame i+1) -- what ``model(x, ...)`` returns for that pair,
+    before composeT or any inversion.  Every frame is encoded once.  BatchNorm as for
+    ``eval_disparity``: the statistics of the n frames by default (the running statistics move), the
+    running statistics after ``model.testmode()``.  Runs on any cached executor of batch >=
+    ceil((n-1)/2) at (H, W) that holds no pending train forward (``Model.eval_executor``).  The
+    result is a copy of the executor-owned output buffer, which the executor's next forward
+    overwrites; like every wrapper here it is enqueued on the current stream without a sync."""
+    n, Cc, H, W = x.shape
+    if Cc != model.encoder.in_channels:
+        raise ValueError("x must be [n, in_channels, H, W]")
+    if n < 2:
+        raise ValueError("eval_pose needs at least two frames")
+    import torch
+    if x.dtype != torch.float32 or x.device.type != "cuda" or not x.is_contiguous():
+        raise ValueError("x must be a contiguous float32 CUDA tensor")
+    if model.depth_decoder.embedding_levels:
+        raise NotImplementedError("eval_pose is not available in MPI mode (embedding_levels > 0)")
+    ex = model.eval_executor(n // 2, H, W)            # n - 1 <= 2 * batch
+    pp = C.c_void_p()
+    ex.forwarded = False            # the library discards any pending forward of this executor
+    check(lib().md2_model_eval_pose(ex.handle, ptr(x), n, C.byref(pp), stream_of(x.device)),
+          "md2_model_eval_pose")
+    if not ex.testmode:
+        ex._trained()
+    return _wrap(pp.value, (n - 1, 6), x.device)
