@@ -74,7 +74,7 @@ int Model::conv_d_bn(RConv& c, int nimg, const float* dy, float* da, long da_bs,
     prof_conv(e, c, s, "dgrad", st);
     return bn_bwd(bn, da, nullptr, y, nimg, HW, dyprev, nullptr, 0, st, true);
   }
-  if (sw.fuse_bn_bwd && bn_bwd_channel_fits(nimg, HW)) {
+  if (sw.fuse_bn_bwd && bn_channel_fits(nimg, HW)) {
     // the slabs are summed in the block's registers: DA (read by this backward alone) is not written
     MD2_TRY(bn_bwd_channel(nullptr, SlabIn{d.slab, d.splits}, nullptr, y, bn.mean, bn.invstd,
                            P(bn.p.g), P(bn.p.b), Gd(bn.p.g), Gd(bn.p.b), nimg, bn.p.c, HW, dyprev,
@@ -114,7 +114,7 @@ int Model::bn_bwd(RBN& bn, const float* dout, const float* mask, const float* y,
   const float* mg = relu_from_y ? P(bn.p.g) : nullptr;
   const float* mb = relu_from_y ? P(bn.p.b) : nullptr;
   if (relu_from_y) mask = nullptr;
-  if (sw.fuse_bn_bwd && bn_bwd_channel_fits(nimg, HW))   // layers 3-4 at the bench shape: one launch
+  if (sw.fuse_bn_bwd && bn_channel_fits(nimg, HW))   // layers 3-4 at the bench shape: one launch
     return bn_bwd_channel(dout, SlabIn{}, mask, y, bn.mean, bn.invstd, P(bn.p.g), mb, Gd(bn.p.g),
                           Gd(bn.p.b), nimg, bn.p.c, HW, dy, dres, dres_acc, st, sk);
   MD2_TRY(bn_bwd_partial(dout, mask, y, bn.mean, bn.invstd, nimg, bn.p.c, HW, w, st, mg, mb, sk));

@@ -25,6 +25,7 @@ Switches Switches::from_env() {
   s.fuse_pool_bwd = env_on("MD2_FUSE_POOL_BWD");
   s.fuse_bnstats = env_on("MD2_FUSE_BNSTATS");
   s.fuse_bn_bwd = env_on("MD2_FUSE_BN_BWD");
+  s.fuse_bn_fwd = env_on("MD2_FUSE_BN_FWD");
   s.fuse_splitk = env_on("MD2_FUSE_SPLITK");
   s.bn_collapse = tuning_knob("MD2_BN_COLLAPSE", 0) != 0;
   s.enc_wgrad_from = tuning_knob("MD2_ENC_WGRAD_FROM", 1);

@@ -54,8 +54,11 @@ int Model::conv_f(RConv& c, int nimg, const TensorIn& in, float* out, long out_b
 // conv + BatchNorm statistics: a split-K conv leaves its slabs to the statistics pass, which
 // sums them (bit-identical to the conv's own reduction), writes y and takes the partials in one
 // launch.  The profile bracket then includes that fused pass (conservative for the roofline).
+// With a tail (the apply that follows) and a channel that fits in a block, statistics and apply
+// are one kernel, from the slabs or from y (MD2_FUSE_BN_FWD; not when the conv's epilogue took the
+// statistics); the bracket then includes the apply as well.
 int Model::conv_f_bn(RConv& c, int nimg, const TensorIn& in, float* y, long out_bs, RBN& bn, long HW,
-                     hipStream_t st, int slot) {
+                     hipStream_t st, int slot, BNTail* tail) {
   const ConvShape s = shape(c, nimg);
   TensorOut o;
   o.p0 = y;
@@ -84,6 +87,16 @@ int Model::conv_f_bn(RConv& c, int nimg, const TensorIn& in, float* y, long out_
       bn.parts = d.stats_parts;
     }
     prof_conv(e, c, s, "fwd", st);
+    return MD2_OK;
+  }
+  if (tail && sw.fuse_bn_fwd && bn_channel_fits(nimg, HW)) {   // layers 3-4 at the bench shape
+    if (tail->join) MD2_HIP(hipStreamWaitEvent(st, tail->join, 0));
+    tail->a.y = y;
+    tail->a.s1 = bn_in(bn);   // (its partials are not read)
+    MD2_TRY(bn_fwd_channel(d.splits > 0 ? SlabIn{d.slab, d.splits} : SlabIn{}, y, tail->a, tail->out,
+                           nimg, bn.p.c, HW, st));
+    prof_conv(e, c, s, "fwd", st);
+    tail->done = true;
     return MD2_OK;
   }
   if (d.splits > 0) {
@@ -160,30 +173,40 @@ int Model::encoder_fwd(const TensorIn& in, int nimg, hipStream_t st) {
       for (size_t k = 0; k < b.st.size(); ++k) {
         EncStage& e = b.st[k];
         const long ohw = (long)e.conv.s.Ho * e.conv.s.Wo;
-        MD2_TRY(conv_f_bn(e.conv, nimg, tin(x, C, HW), e.y, (long)e.conv.p.cout * ohw, e.bn, ohw, st));
-        if (k + 1 < b.st.size()) {
-          BNApplyFused a{};
-          a.y = e.y; a.s1 = bn_in(e.bn); a.relu = 1;
-          MD2_TRY(bn_apply_fused(a, e.a, nimg, e.conv.p.cout, ohw, st));
+        const bool last = k + 1 == b.st.size();
+        // the apply after this conv's BN: BN + ReLU inside the block; the block's last one adds
+        // the identity residual or the downsample branch's BN before the ReLU
+        BNTail t;
+        t.out = e.a;
+        t.a.relu = 1;
+        if (last && !b.down) t.a.res = b.in;
+        // The one-kernel forward reads yd, so the branch is enqueued before the conv (on the side
+        // stream it is already) and the wait for it moves in front of that kernel.
+        bool down_ready = false;
+        if (last && b.down && sw.fuse_bn_fwd && bn_channel_fits(nimg, ohw)) {
+          if (dov)
+            t.join = ov.join_ev;
+          else
+            MD2_TRY(down_fwd(b, nimg, st));
+          t.a.y2 = b.yd; t.a.s2 = bn_in(b.dbn);
+          down_ready = true;
+        }
+        MD2_TRY(conv_f_bn(e.conv, nimg, tin(x, C, HW), e.y, (long)e.conv.p.cout * ohw, e.bn, ohw, st, 0, &t));
+        if (!t.done) {   // statistics taken by conv_f_bn: the apply pass
+          if (last && b.down) {
+            if (dov)
+              MD2_HIP(hipStreamWaitEvent(st, ov.join_ev, 0));
+            else if (!down_ready)
+              MD2_TRY(down_fwd(b, nimg, st));
+            t.a.y2 = b.yd; t.a.s2 = bn_in(b.dbn);
+          }
+          t.a.y = e.y; t.a.s1 = bn_in(e.bn);
+          MD2_TRY(bn_apply_fused(t.a, t.out, nimg, e.conv.p.cout, ohw, st));
         }
         x = e.a;
         C = e.conv.p.cout;
         HW = ohw;
       }
-      EncStage& last = b.st.back();
-      const long ohw = (long)b.H * b.W;
-      BNApplyFused a{};
-      a.y = last.y; a.s1 = bn_in(last.bn); a.relu = 1;
-      if (b.down) {
-        if (dov)
-          MD2_HIP(hipStreamWaitEvent(st, ov.join_ev, 0));
-        else
-          MD2_TRY(down_fwd(b, nimg, st));
-        a.y2 = b.yd; a.s2 = bn_in(b.dbn);
-      } else {
-        a.res = b.in;
-      }
-      MD2_TRY(bn_apply_fused(a, last.a, nimg, b.C, ohw, st));
     }
   return MD2_OK;
 }

@@ -35,6 +35,15 @@ struct RBN {
   int parts = 0;
   float *ts = nullptr, *tt = nullptr;   // test mode: the folded affine map (s, t)
 };
+// The apply that follows a conv's BatchNorm, handed to conv_f_bn: where a channel fits in a block
+// (bn_channel_fits) statistics and apply are one kernel there, and `done` says so; otherwise the
+// caller runs bn_apply_fused as before.  a.y and a.s1 are conv_f_bn's to fill.
+struct BNTail {
+  BNApplyFused a;
+  float* out = nullptr;
+  hipEvent_t join = nullptr;   // the side stream's event behind a.y2, awaited before the one kernel
+  bool done = false;
+};
 struct EncStage {
   RConv conv;
   RBN bn;
@@ -77,7 +86,10 @@ struct Switches {
   // 0: the two-pass BN backward (partials + apply) where a channel fits in one block of
   // bn_bwd_channel (closeness test: the fp64 sums run in another order)
   bool fuse_bn_bwd;
-  bool fuse_splitk;      // 0: the separate reduction launches (A/B measurement)
+  // 0: the two-pass BN forward (statistics partials + apply) where a channel fits in one block of
+  // bn_fwd_channel and the conv took no statistics in its epilogue (closeness test, as above)
+  bool fuse_bn_fwd;
+  bool fuse_splitk;     // 0: the separate reduction launches (A/B measurement)
   bool bn_collapse;      // MD2_BN_COLLAPSE=1: one collapse launch first -- measured slower, 6 us per launch
   // (round 6, with the LDS-halo kernels: from layer 2 (si = 1) 6.194 vs 6.211 ms and 6.159 vs 6.19
   // against layer 4 only, interleaved; from layer 1 6.167)
@@ -340,7 +352,7 @@ class Model {
   int conv_f(RConv& c, int nimg, const TensorIn& in, float* out, long out_bs, int act, hipStream_t st,
              const float* wp = nullptr, const float* bias = nullptr);
   int conv_f_bn(RConv& c, int nimg, const TensorIn& in, float* y, long out_bs, RBN& bn, long HW,
-                hipStream_t st, int slot = 0);
+                hipStream_t st, int slot = 0, BNTail* tail = nullptr);
   BNStatsWs bn_ws(RBN& bn, int nimg, long HW, int slot);
   int bn_fwd(RBN& bn, const float* y, int nimg, long HW, hipStream_t st, int slot = 0);
   BNStatsIn bn_in(const RBN& bn);

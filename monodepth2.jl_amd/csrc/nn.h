@@ -66,6 +66,19 @@ int bn_stats_partial(const float* y, int N, int C, long HW, BNStatsWs ws, hipStr
 int bn_partials_collapse(const double* part, int C, int parts, double* out, hipStream_t st);
 int bn_stats_partial_slabs(SlabIn sl, float* y, int N, int C, long HW, BNStatsWs ws, hipStream_t st);
 int bn_apply_fused(const BNApplyFused& p, float* out, int N, int C, long HW, hipStream_t st);
+// A channel fits in one block of the one-kernel BN passes below (bn_fwd_channel, bn_bwd_channel):
+// HW % 4 == 0 and N*HW/4 float4 units within a 1024-thread block's registers (8192 values).  One
+// predicate, so a layer's forward and backward always agree.
+bool bn_channel_fits(int N, long HW);
+// Statistics + apply in one launch for such a BN: bn_stats_partial[_slabs] + bn_apply_fused with y
+// read once.  The input is p.y, or sl (the conv's split-K slabs, summed in split order into y,
+// which is written bit-identically to bn_stats_partial_slabs'; p.y is not read).  p.s1's partials
+// are not used: the block sums the channel in fp64 in its own fixed order and finalises with
+// bn_apply_fused's code (mean / invstd / running statistics stored once per channel) -- mean and
+// invstd within an ulp of the two passes, not bitwise.  p.y2 / p.s2 (the downsample branch, from
+// its own statistics partials), p.res and p.relu as in bn_apply_fused.
+int bn_fwd_channel(SlabIn sl, float* y, const BNApplyFused& p, float* out, int N, int C, long HW,
+                   hipStream_t st);
 // backward reduce: g = dout * (mask_out > 0 if mask_out) ; dgamma = sum g*xhat, dbeta = sum g
 int bn_bwd_reduce(const float* dout, const float* mask_out, const float* y, const float* mean,
                   const float* invstd, int N, int C, long HW, float* dgamma, float* dbeta,
@@ -86,13 +99,11 @@ int bn_bwd_apply_fused(const float* dout, const float* mask_out, const float* y,
                        float* dbeta, int N, int C, long HW, float* dy, float* dres,
                        int dres_accumulate, hipStream_t st, const float* mbeta = nullptr,
                        SkipAdd sk = SkipAdd{});
-// The whole backward in one launch for a BN whose channel fits in a block (HW % 4 == 0 and
-// N*HW/4 float4 units within a 256-thread block's registers): partial sums, dgamma/dbeta and the
-// apply, each tensor read once.  dout, or sl (the dgrad's split-K slabs, summed in split order;
-// dout == nullptr, no mask_out / sk, nothing but dy written); mask_out / mbeta / sk / dres as in
-// the two passes.  The fp64 sums run in the block's own fixed order: last-bit differences to the
-// two passes at most.
-bool bn_bwd_channel_fits(int N, long HW);
+// The whole backward in one launch for a BN whose channel fits in a block (bn_channel_fits):
+// partial sums, dgamma/dbeta and the apply, each tensor read once.  dout, or sl (the dgrad's
+// split-K slabs, summed in split order; dout == nullptr, no mask_out / sk, nothing but dy
+// written); mask_out / mbeta / sk / dres as in the two passes.  The fp64 sums run in the block's
+// own fixed order: last-bit differences to the two passes at most.
 int bn_bwd_channel(const float* dout, SlabIn sl, const float* mask_out, const float* y,
                    const float* mean, const float* invstd, const float* gamma, const float* mbeta,
                    float* dgamma, float* dbeta, int N, int C, long HW, float* dy, float* dres,

@@ -262,6 +262,30 @@ int bn_apply(const BNApply& p, float* out, int N, int C, long HW, hipStream_t st
 // planes pl0+w, pl0+w+4, ... from the partials (lane-parallel fixed-order sum + wave reduction,
 // same result in every block), the scale/shift go through LDS.  The block holding the first unit of image 0's plane of channel c writes mean[c],
 // invstd[c] and the running statistics.
+// From a channel's fp64 sums (a = sum y, aa = sum y^2 over `total` values) to the scale / shift of
+// the apply; the thread with `store` set writes mean, invstd and the running statistics.  The one
+// copy of these roundings: bn_finalise_plane and bn_fwd_channel_kernel both end here, and the
+// backward re-derives the ReLU mask from y with the same operations.
+__device__ __forceinline__ void bn_finalise_sums(const BNStatsIn& s, int c, double a, double aa,
+                                                 double total, bool store, float& sc, float& sh) {
+  const double mu = a / total;
+  const double var = fmax(aa / total - mu * mu, 0.0);
+  const float meanf = (float)mu;
+  const float isf = (float)(1.0 / sqrt(var + (double)s.eps));
+  // explicit roundings: bn_bwd_* re-derive relu(y*sc + sh) > 0 from y with the same operations
+  sc = __fmul_rn(s.gamma[c], isf);
+  sh = __fmaf_rn(-meanf, sc, s.beta[c]);
+  if (store) {
+    s.mean[c] = meanf;
+    s.invstd[c] = isf;
+    if (s.run_mean) {
+      const float m = s.momentum;
+      s.run_mean[c] = (1.f - m) * s.run_mean[c] + m * meanf;
+      s.run_var[c] = (1.f - m) * s.run_var[c] + m * (float)(var * total / fmax(total - 1.0, 1.0));
+    }
+  }
+}
+
 // called by a whole wave: lane l sums partials l, l+64, ... (fixed order), then a wave reduction
 // -- one partial-load latency per plane instead of `parts` dependent ones
 __device__ __forceinline__ void bn_finalise_plane(const BNStatsIn& s, int c, double total,
@@ -274,22 +298,7 @@ __device__ __forceinline__ void bn_finalise_plane(const BNStatsIn& s, int c, dou
   }
   a = wave_sum_d(a);
   aa = wave_sum_d(aa);
-  const double mu = a / total;
-  const double var = fmax(aa / total - mu * mu, 0.0);
-  const float meanf = (float)mu;
-  const float isf = (float)(1.0 / sqrt(var + (double)s.eps));
-  // explicit roundings: bn_bwd_* re-derive relu(y*sc + sh) > 0 from y with the same operations
-  sc = __fmul_rn(s.gamma[c], isf);
-  sh = __fmaf_rn(-meanf, sc, s.beta[c]);
-  if (owner && (threadIdx.x & 63) == 0) {
-    s.mean[c] = meanf;
-    s.invstd[c] = isf;
-    if (s.run_mean) {
-      const float m = s.momentum;
-      s.run_mean[c] = (1.f - m) * s.run_mean[c] + m * meanf;
-      s.run_var[c] = (1.f - m) * s.run_var[c] + m * (float)(var * total / fmax(total - 1.0, 1.0));
-    }
-  }
+  bn_finalise_sums(s, c, a, aa, total, owner && (threadIdx.x & 63) == 0, sc, sh);
 }
 
 // Units per thread of the fused apply passes: a block covers 256 * UPT consecutive units, so the
@@ -980,7 +989,7 @@ __global__ __launch_bounds__(BN_CH_THREADS) void bn_bwd_channel_kernel(
   }
 }
 
-bool bn_bwd_channel_fits(int N, long HW) {
+bool bn_channel_fits(int N, long HW) {
   return HW % 4 == 0 && (long)N * (HW / 4) <= (long)BN_CH_THREADS * BN_CH_UNITS;
 }
 
@@ -990,7 +999,7 @@ int bn_bwd_channel(const float* dout, SlabIn sl, const float* mask_out, const fl
                    int dres_accumulate, hipStream_t st, SkipAdd sk) {
   const long n = (long)N * C * HW;
   MD2_TRY(check_u31(n));
-  MD2_CHECK_ARG(bn_bwd_channel_fits(N, HW), "bn_bwd_channel: a channel must fit in a block");
+  MD2_CHECK_ARG(bn_channel_fits(N, HW), "bn_bwd_channel: a channel must fit in a block");
   MD2_CHECK_ARG((sl.slab != nullptr) != (dout != nullptr) &&
                     (!sl.slab || (sl.splits >= 1 && !sk.skip && !mask_out)),
                 "bn_bwd_channel: dout or slabs (slabs without skip / mask tensor)");
@@ -1004,6 +1013,140 @@ int bn_bwd_channel(const float* dout, SlabIn sl, const float* mask_out, const fl
   else if (sk.skip) MD2_BWDC(false, true);
   else MD2_BWDC(false, false);
 #undef MD2_BWDC
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
+// ---- the forward twin: statistics and apply of a BN whose channel fits in a block, in one
+// kernel.  The block takes the channel's y into registers (SLAB: formed from the conv's split-K
+// slabs in split order, as bn_stats_partial_kernel<.., SLAB> forms it, and stored -- the backward
+// reads it), sums y and y^2 in fp64 (a thread's units in order, wave reduction, the 16 waves in
+// order: one barrier), finalises through bn_finalise_sums like every other BN forward and applies
+// with bn_apply_fused_kernel's expressions: y is read once and the partials never leave the block.
+// The downsample branch's BN (p.y2) keeps its own statistics pass; its partials are finalised here
+// by the last wave, behind the loads, and reach the others through the same barrier.  Thread 0
+// and that wave's lane 0 are the owners of the channel's mean / invstd / running statistics.
+template <bool SLAB>
+__global__ __launch_bounds__(BN_CH_THREADS) void bn_fwd_channel_kernel(
+    BNApplyFused p, float* yout, float* __restrict__ out, int C, int N, FastDiv fdu, double total,
+    SlabIn sl) {
+  constexpr int NW = BN_CH_THREADS / 64;
+  __shared__ double red[2 * NW];
+  __shared__ float s_two[2];
+  const int c = blockIdx.x;
+  const uint32_t U = fdu.d, HW = 4u * U, nu = (uint32_t)N * U;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float4 v[BN_CH_UNITS], q2[BN_CH_UNITS], qr[BN_CH_UNITS];
+  uint32_t off[BN_CH_UNITS];
+  // every load of the channel in flight before the first is used
+#pragma unroll
+  for (int h = 0; h < BN_CH_UNITS; ++h) {
+    const uint32_t e = threadIdx.x + (uint32_t)BN_CH_THREADS * h;
+    v[h] = q2[h] = qr[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    off[h] = 0;
+    if (e >= nu) continue;
+    const uint32_t im = fdiv(e, fdu), k = e - im * U;
+    const uint32_t i = (im * (uint32_t)C + (uint32_t)c) * HW + 4u * k;
+    off[h] = i;
+    if (!SLAB) v[h] = *reinterpret_cast<const float4*>(p.y + i);
+    if (p.y2) q2[h] = *reinterpret_cast<const float4*>(p.y2 + i);
+    if (p.res) qr[h] = *reinterpret_cast<const float4*>(p.res + i);
+  }
+  if (SLAB) {
+    // split by split, a split's units all in flight; each element adds its slabs to 0 in split order
+    const long sstride = (long)C * N * HW;
+    const float* sq = sl.slab + (long)c * N * HW;
+    for (int q = 0; q < sl.splits; ++q, sq += sstride) {
+      float4 t[BN_CH_UNITS];
+#pragma unroll
+      for (int h = 0; h < BN_CH_UNITS; ++h) {
+        const uint32_t e = threadIdx.x + (uint32_t)BN_CH_THREADS * h;   // slab plane [N][HW]: 4 * e
+        if (e < nu) t[h] = *reinterpret_cast<const float4*>(sq + 4u * e);
+      }
+#pragma unroll
+      for (int h = 0; h < BN_CH_UNITS; ++h) {
+        if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+        v[h].x += t[h].x; v[h].y += t[h].y; v[h].z += t[h].z; v[h].w += t[h].w;
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < BN_CH_UNITS; ++h) {
+      if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+      *reinterpret_cast<float4*>(yout + off[h]) = v[h];
+    }
+  }
+  if (p.y2 && wid == NW - 1) {   // wave-uniform
+    float a2, b2;
+    bn_finalise_plane(p.s2, c, total, true, a2, b2);
+    if (lane == 0) {
+      s_two[0] = a2;
+      s_two[1] = b2;
+    }
+  }
+  double s = 0.0, ss = 0.0;
+#pragma unroll
+  for (int h = 0; h < BN_CH_UNITS; ++h) {
+    if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+    const float4 w = v[h];
+    s += (double)w.x + (double)w.y + (double)w.z + (double)w.w;
+    ss += (double)w.x * w.x + (double)w.y * w.y + (double)w.z * w.z + (double)w.w * w.w;
+  }
+  s = wave_sum_d(s);
+  ss = wave_sum_d(ss);
+  if (lane == 0) {
+    red[wid] = s;
+    red[NW + wid] = ss;
+  }
+  __syncthreads();
+  double ts = red[0], tss = red[NW];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+    ts += red[w];
+    tss += red[NW + w];
+  }
+  float sc, sh;
+  bn_finalise_sums(p.s1, c, ts, tss, total, threadIdx.x == 0, sc, sh);
+  float sc2 = 0.f, sh2 = 0.f;
+  if (p.y2) {
+    sc2 = s_two[0];
+    sh2 = s_two[1];
+  }
+#pragma unroll
+  for (int h = 0; h < BN_CH_UNITS; ++h) {
+    if (threadIdx.x + (uint32_t)BN_CH_THREADS * h >= nu) continue;
+    float r[4] = {__fmaf_rn(v[h].x, sc, sh), __fmaf_rn(v[h].y, sc, sh), __fmaf_rn(v[h].z, sc, sh),
+                  __fmaf_rn(v[h].w, sc, sh)};
+    if (p.y2) {
+      const float4 q = q2[h];
+      r[0] += q.x * sc2 + sh2; r[1] += q.y * sc2 + sh2; r[2] += q.z * sc2 + sh2; r[3] += q.w * sc2 + sh2;
+    }
+    if (p.res) {
+      const float4 q = qr[h];
+      r[0] += q.x; r[1] += q.y; r[2] += q.z; r[3] += q.w;
+    }
+    if (p.relu) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k] = fmaxf(r[k], 0.f);
+    }
+    *reinterpret_cast<float4*>(out + off[h]) = make_float4(r[0], r[1], r[2], r[3]);
+  }
+}
+
+int bn_fwd_channel(SlabIn sl, float* y, const BNApplyFused& p, float* out, int N, int C, long HW,
+                   hipStream_t st) {
+  MD2_TRY(check_u31((long)N * C * HW));
+  MD2_CHECK_ARG(bn_channel_fits(N, HW), "bn_fwd_channel: a channel must fit in a block");
+  MD2_CHECK_ARG(out && (sl.slab ? sl.splits >= 1 && y != nullptr : p.y != nullptr),
+                "bn_fwd_channel: y, or slabs and the y they are summed into");
+  MD2_CHECK_ARG(p.s1.gamma && p.s1.beta && p.s1.mean && p.s1.invstd, "bn_fwd_channel: BN operands");
+  MD2_CHECK_ARG(!p.y2 || (p.s2.part && p.s2.parts >= 1), "bn_fwd_channel: missing statistics partials");
+  const double total = (double)((long)N * HW);
+  if (sl.slab)
+    hipLaunchKernelGGL(bn_fwd_channel_kernel<true>, dim3(C), dim3(BN_CH_THREADS), 0, st, p, y, out, C,
+                       N, fd(HW / 4), total, sl);
+  else
+    hipLaunchKernelGGL(bn_fwd_channel_kernel<false>, dim3(C), dim3(BN_CH_THREADS), 0, st, p, y, out,
+                       C, N, fd(HW / 4), total, sl);
   MD2_LAUNCH_CHECK();
   return MD2_OK;
 }
