@@ -769,6 +769,87 @@ int md2_pose_eval(const float* pred,            /* device [M][6]                
                   float* rt_out,                /* device [M][12] or NULL                         */
                   void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Guarded optimiser step: the global L2 norm of the flat gradient, clipping by it, and "skip the
+ * update if any gradient entry is non-finite" -- between the backward and ADAM, entirely on the
+ * device, without a host synchronisation.  Additive: MD2_ABI_VERSION is unchanged.  With the guard
+ * off nothing changes; with it on, max_norm = +inf and finite gradients the step writes the same
+ * bytes as the plain step.
+ *
+ * md2_grad_norm: two launches over any flat fp32 device vector g[0..n), 1 <= n <= 2^31.
+ *  1. grad_sumsq.  S = the fp64 sum of (double)g_i * (double)g_i over the FINITE entries (each
+ *     product is exact in fp64), c = the number of non-finite entries (NaN, +Inf, -Inf), which add
+ *     nothing to S.  The order is defined on element indices alone:
+ *       B = min(ceil(n / 4096), 1024) blocks of 256 threads (the grid depends on n only);
+ *       thread t of block k adds the elements 4 (256 k + t) + j (1024 B) + {0, 1, 2, 3} that lie
+ *       below n, for j = 0, 1, ... ascending and the four in index order, one after the other into
+ *       one fp64 accumulator that starts at 0;
+ *       the 64 lanes of a wave are combined by a butterfly (partner lane ^ 32, 16, 8, 4, 2, 1), the
+ *       four waves as (w0 + w1) + (w2 + w3);
+ *       block k writes its partial and its count to the workspace.
+ *     A 16-byte aligned g is read with 16-byte loads, any other with 4-byte loads; the map from
+ *     elements to threads is the same, so the result does not depend on the pointer's alignment.
+ *  2. grad_guard_finish, one block of 256 threads: thread t adds the block partials t, t + 256, ...
+ *     ascending into an accumulator that starts at 0; the same butterfly and wave order follow.
+ *     Thread 0 then writes *state:
+ *       sumsq = S;  nonfinite = c;  ok = (c == 0);
+ *       norm  = (float)(sqrt(S) * (double)grad_scale)    (fp64 square root and product, one rounding
+ *               to fp32): the norm of the gradient ADAM will see, grad_scale * g;
+ *       coef  = max_norm / norm when ok, max_norm is finite and norm > max_norm, otherwise 1.0f:
+ *               ONE correctly rounded fp32 division.  This is NOT torch's clip_grad_norm_ coefficient
+ *               max_norm / (norm + 1e-6): a gradient of exactly max_norm is left alone, and a
+ *               clipped one has norm max_norm to one rounding;
+ *       gscale = grad_scale * coef, one fp32 multiply (coef == 1 gives grad_scale bit for bit);
+ *       skipped += !ok: cumulative, read-modify-written -- the caller zeroes *state once.
+ * No atomics, no "last block" counter: BITWISE REPRODUCIBLE.  No allocation, no host
+ * synchronisation.  The workspace (md2_grad_norm_workspace_size(n) bytes of device memory, 8-byte
+ * aligned; 0 for n outside 1..2^31) may hold anything on entry.  max_norm = +inf: no clipping.
+ * MD2_EINVAL (checked before any HIP call): a null g, state or workspace; n outside 1..2^31;
+ * max_norm NaN or <= 0; grad_scale not finite and positive; a workspace not 8-byte aligned.
+ *
+ * md2_adam_guarded: md2_adam driven by a state block.  When !state->ok every thread returns before
+ * any load or store of p, adam_m, adam_v; otherwise the arithmetic is md2_adam's with
+ * grad_scale = state->gscale (same expressions, same order, same bits).
+ *
+ * md2_model_set_grad_guard(m, on, max_norm): model state (max_norm as above; ignored when on = 0).
+ * While the guard is on, md2_model_adam, md2_model_train_step, md2_model_train_step_graph (and _aug)
+ * and md2_model_train_step_dp run md2_grad_norm over the whole flat gradient -- in the DP step after
+ * the last bucket's all-reduce, with grad_scale = 1/nranks -- then the guarded ADAM and the re-pack.
+ * md2_model_adam_segment returns MD2_ENOTSUP (a segment's update cannot know the global norm) and
+ * the MD2_SEG_UPDATE=1 routes take the single update.  (on, max_norm) is part of the captured
+ * step's re-capture key.  The state and the workspace are executor-owned, allocated when the guard
+ * is first switched on and counted in md2_model_device_bytes from then on.  Every call clears
+ * `skipped` (and the rest of the state); it synchronises the device to do so, so it belongs
+ * outside the step.  Test mode: MD2_ESTATE, like the other training entries; MPI mode
+ * (embedding_levels > 0): MD2_ENOTSUP.
+ * Step counting: a skipped step still consumes its step number -- the bias correction uses the
+ * caller's `step`, and in the captured step the device counter advances unconditionally -- so the
+ * eager and the captured path stay bit-equal and the host never needs to know that a step was
+ * skipped.  A skipped step leaves params, adam_m, adam_v unchanged; the re-pack then rewrites the
+ * packed weights with the values they already hold.
+ * BatchNorm running statistics move in the forward, before the gradient exists: a skipped step
+ * does NOT undo that.
+ * md2_model_grad_guard_state: the device pointer of the executor's state; its values are those of
+ * the last guarded step once the stream has passed it.  MD2_ESTATE if the guard was never on.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct md2_guard_state {
+  double sumsq;          /* S: the fp64 sum of squares of the finite entries              */
+  long long nonfinite;   /* c: the number of NaN / Inf entries                            */
+  long long skipped;     /* steps with ok == 0 since the state was last zeroed            */
+  float norm;            /* (float)(sqrt(S) * grad_scale)                                 */
+  float coef;            /* the clip coefficient, 1.0f when nothing is clipped            */
+  float gscale;          /* grad_scale * coef: what the guarded ADAM multiplies g by      */
+  int ok;                /* c == 0                                                        */
+} md2_guard_state;
+size_t md2_grad_norm_workspace_size(long long n);
+int md2_grad_norm(const float* g, long long n, float grad_scale, float max_norm,
+                  md2_guard_state* state /* device */, void* workspace, void* stream);
+int md2_adam_guarded(float* p, const float* g, float* adam_m, float* adam_v, long long n, float lr,
+                     float beta1, float beta2, float eps, int step,
+                     const md2_guard_state* state /* device */, void* stream);
+int md2_model_set_grad_guard(md2_model* m, int on, float max_norm);
+int md2_model_grad_guard_state(md2_model* m, const md2_guard_state** dev);
+
 #ifdef __cplusplus
 }
 #endif

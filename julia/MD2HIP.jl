@@ -515,6 +515,34 @@ function update!(m::HIPModel, η; β=(0.9f0, 0.999f0), ϵ=1f-8, grad_scale=1f0)
     return m
 end
 
+"""
+    set_grad_guard(m::HIPModel, on::Bool; max_norm=Inf32)
+    grad_guard_state(m::HIPModel)
+
+The guarded optimiser step (md2_model_set_grad_guard).  While on, `update!`, `train_step!` and the
+captured and data-parallel steps measure the global L2 norm of ∇θ on the device, clip it to
+`max_norm` (`Inf32`: no clipping) and leave θ and the ADAM moments untouched when a gradient entry is
+NaN or Inf.  A skipped step still counts in `m.step`; BatchNorm running statistics moved in the
+forward stay moved.  Switching clears `skipped` and synchronises the device.
+
+`grad_guard_state` copies the 40-byte device state to the host (this synchronises) and returns
+`(norm, coef, ok, skipped, nonfinite)` of the last guarded step.
+"""
+function set_grad_guard(m::HIPModel, on::Bool; max_norm=Inf32)
+    check(ccall((:md2_model_set_grad_guard, lib), Cint, (Ptr{Cvoid}, Cint, Cfloat),
+                m.handle, on ? 1 : 0, Float32(max_norm)))
+    return m
+end
+
+function grad_guard_state(m::HIPModel)
+    p = Ref{Ptr{UInt8}}(C_NULL)
+    check(ccall((:md2_model_grad_guard_state, lib), Cint, (Ptr{Cvoid}, Ptr{Ptr{UInt8}}), m.handle, p))
+    raw = Array(unsafe_wrap(ROCArray, p[], (40,)))         # md2_guard_state: f64, i64, i64, 3 x f32, i32
+    f(T, off) = reinterpret(T, raw[off + 1:off + sizeof(T)])[1]
+    return (norm=f(Float32, 24), coef=f(Float32, 28), ok=f(Int32, 36) != 0, skipped=f(Int64, 16),
+            nonfinite=f(Int64, 8))
+end
+
 # eval_disparity(m, x) -- src/model.jl:63; x::(W,H,C,n), n <= batch
 function eval_disparity(m::HIPModel, x::ROCArray{Float32,4})
     d = Vector{Ptr{Float32}}(undef, 5)

@@ -296,6 +296,29 @@ int md2_adam(float* p, const float* g, float* adam_m, float* adam_v, long long n
                    grad_scale, (hipStream_t)stream);
 }
 
+// ---- gradient guard ----------------------------------------------------------------------------
+size_t md2_grad_norm_workspace_size(long long n) { return grad_norm_workspace_bytes(n); }
+
+int md2_grad_norm(const float* g, long long n, float grad_scale, float max_norm, md2_guard_state* state,
+                  void* workspace, void* stream) {
+  // validation first, without a HIP call
+  MD2_CHECK_ARG(g && state && workspace, "grad_norm: null pointer");
+  MD2_CHECK_ARG(n >= 1 && n <= (1LL << 31), "grad_norm: n must be in 1..2^31");
+  MD2_CHECK_ARG(max_norm > 0.f, "grad_norm: max_norm must be positive (+inf: no clipping)");   // false for NaN
+  MD2_CHECK_ARG(std::isfinite(grad_scale) && grad_scale > 0.f, "grad_norm: grad_scale must be finite and positive");
+  MD2_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "grad_norm: the workspace must be 8-byte aligned");
+  return grad_norm(g, n, grad_scale, max_norm, state, workspace, (hipStream_t)stream);
+}
+
+int md2_adam_guarded(float* p, const float* g, float* adam_m, float* adam_v, long long n, float lr,
+                     float beta1, float beta2, float eps, int step, const md2_guard_state* state,
+                     void* stream) {
+  MD2_CHECK_ARG(p && g && adam_m && adam_v && state && n > 0 && step >= 1, "adam_guarded args");
+  const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
+  return adam_step_guarded(p, g, adam_m, adam_v, (long)n, lr, beta1, beta2, eps, (float)bc1, (float)bc2,
+                           state, (hipStream_t)stream);
+}
+
 // ---- pooling / resampling --------------------------------------------------------------------
 int md2_maxpool3s2_fwd(const float* x, int n, int c, int h, int w, float* y, unsigned char* arg,
                        void* stream) {
@@ -521,7 +544,8 @@ int md2_model_train_step(md2_model* m, const float* x, const float* auto_loss, f
   MD2_CHECK_ARG(m && adam_m && adam_v && step >= 1, "train_step args");
   hipStream_t st = (hipStream_t)stream;
   MD2_TRY(model_forward_loss(m->impl, x, auto_loss, loss, nullptr, st));
-  if (!model_segment_update_enabled()) {   // measured default: one update after the backward
+  // measured default: one update after the backward (the gradient guard needs the whole gradient)
+  if (!model_segment_update_enabled() || model_grad_guard_on(m->impl)) {
     for (int k = 0; k < model_num_segments(m->impl); ++k)
       MD2_TRY(model_backward_segment(m->impl, k, nullptr, nullptr, st));
     return model_adam(m->impl, adam_m, adam_v, lr, 0.9f, 0.999f, 1e-8f, step, 1.f, st);
@@ -546,6 +570,16 @@ int md2_model_train_step_graph_aug(md2_model* m, const float* x, const float* x_
   MD2_CHECK_ARG(m, "model");
   return model_train_step_graph_aug(m->impl, x, x_net, auto_loss, adam_m, adam_v, lr, step, loss,
                                     (hipStream_t)stream);
+}
+
+int md2_model_set_grad_guard(md2_model* m, int on, float max_norm) {
+  MD2_CHECK_ARG(m, "model");
+  return model_set_grad_guard(m->impl, on, max_norm);
+}
+
+int md2_model_grad_guard_state(md2_model* m, const md2_guard_state** dev) {
+  MD2_CHECK_ARG(m, "model");
+  return model_grad_guard_state(m->impl, dev);
 }
 
 int md2_model_set_params(md2_model* m, const float* flux, void* stream) {

@@ -104,7 +104,7 @@ int model_num_segments(Model* m) { return m ? 6 : 0; }
 // Graph-captured train step (forward + loss + every backward segment + ADAM + weight repack as
 // ONE hipGraph): the ~320 launches of a step replay without per-launch host work.  Captured on
 // the executor's own stream on first use (and again when adam_m / adam_v / lr / the presence of
-// the automask input or of x_net change); each call copies x (and auto_loss, x_net) into the
+// the automask input or of x_net, or the gradient guard's (on, max_norm) change); each call copies x (and auto_loss, x_net) into the
 // executor's input buffers, replays
 // on `st`, and copies the loss out.  ADAM's step count lives on the device (adam_prep), re-set
 // only when the caller's `step` is not the one the graph expects next.
@@ -132,9 +132,16 @@ static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, 
     m->cot_ready = 1;
     MD2_TRY(m->forward_loss(g.x, net, with_auto ? g.autoloss : nullptr, g.loss, nullptr, g.st));
     for (int k = 0; k < model_num_segments(m); ++k) MD2_TRY(model_backward_segment(m, k, nullptr, nullptr, g.st));
+    // the step counter advances whether or not the guard lets the update through (md2.h)
     MD2_TRY(adam_prep(g.step, g.bc, 0.9f, 0.999f, g.st));
-    MD2_TRY(adam_step_dev(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, 0.9f, 0.999f, 1e-8f,
-                          g.bc, 1.f, g.st));
+    if (m->gd.on) {
+      MD2_TRY(grad_norm(m->grads, m->spec.total, 1.f, m->gd.max_norm, m->gd.state, m->gd.ws, g.st));
+      MD2_TRY(adam_step_dev_guarded(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, 0.9f, 0.999f,
+                                    1e-8f, g.bc, m->gd.state, g.st));
+    }
+    else
+      MD2_TRY(adam_step_dev(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, 0.9f, 0.999f, 1e-8f,
+                            g.bc, 1.f, g.st));
     return m->repack(g.st);
   };
   const int rc = body();
@@ -153,6 +160,8 @@ static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, 
   g.lr = lr;
   g.with_auto = with_auto ? 1 : 0;
   g.with_net = with_net ? 1 : 0;
+  g.guard_on = m->gd.on ? 1 : 0;
+  g.guard_max = m->gd.max_norm;
   g.next_step = -1;
   return MD2_OK;
 }
@@ -175,7 +184,8 @@ int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, con
   // pending per-segment updates (outside the capture: the event lives outside the graph)
   MD2_TRY(m->adam_join(st));
   if (!g.exec || g.adam_m != adam_m || g.adam_v != adam_v || g.lr != lr || g.with_auto != (int)with_auto ||
-      g.with_net != (int)with_net)
+      g.with_net != (int)with_net || g.guard_on != (int)m->gd.on ||
+      (m->gd.on && g.guard_max != m->gd.max_norm))
     MD2_TRY(capture_step(m, with_auto, with_net, adam_m, adam_v, lr));
   const size_t xb = sizeof(float) * (size_t)m->N * 3 * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W;
   if (x != g.x) MD2_HIP(hipMemcpyAsync(g.x, x, xb, hipMemcpyDeviceToDevice, st));
@@ -257,9 +267,55 @@ int model_adam(Model* m, float* adam_m, float* adam_v, float lr, float b1, float
   MD2_TRY(refuse_testmode(m, "adam"));
   MD2_TRY(m->adam_join(st));   // pending per-segment updates (model_adam_segment)
   const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
-  MD2_TRY(adam_step(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, b1, b2, eps, (float)bc1,
-                    (float)bc2, grad_scale, st));
+  if (m->gd.on) {
+    MD2_CHECK_ARG(std::isfinite(grad_scale) && grad_scale > 0.f, "guarded adam: grad_scale must be finite and positive");
+    MD2_TRY(grad_norm(m->grads, m->spec.total, grad_scale, m->gd.max_norm, m->gd.state, m->gd.ws, st));
+    MD2_TRY(adam_step_guarded(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, b1, b2, eps, (float)bc1,
+                              (float)bc2, m->gd.state, st));
+  }
+  else
+    MD2_TRY(adam_step(m->params, m->grads, adam_m, adam_v, m->spec.total, lr, b1, b2, eps, (float)bc1,
+                      (float)bc2, grad_scale, st));
   return m->repack(st);
+}
+
+// ---- gradient guard
+int model_set_grad_guard(Model* m, int on, float max_norm) {
+  MD2_CHECK_ARG(m, "model");
+  MD2_TRY(refuse_testmode(m, "set_grad_guard"));
+  if (m->E > 0) {
+    set_error("set_grad_guard: not available in MPI mode (embedding_levels > 0)");
+    return MD2_ENOTSUP;
+  }
+  if (on) {
+    MD2_CHECK_ARG(max_norm > 0.f, "set_grad_guard: max_norm must be positive (+inf: no clipping)");   // false for NaN
+    MD2_CHECK_ARG(m->spec.total >= 1 && m->spec.total <= (1LL << 31), "set_grad_guard: parameter count");
+    if (!m->gd.state) {
+      MD2_TRY(m->alloc(&m->gd.state, 1));
+      MD2_TRY(m->alloc_bytes(&m->gd.ws, 1, grad_norm_workspace_bytes(m->spec.total), true));
+    }
+  }
+  if (m->gd.state) {
+    // `skipped` starts again; the device is idle around the write, so no stream can be mid-step
+    MD2_HIP(hipDeviceSynchronize());
+    MD2_HIP(hipMemset(m->gd.state, 0, sizeof(md2_guard_state)));
+    MD2_HIP(hipDeviceSynchronize());
+  }
+  m->gd.on = on != 0;
+  if (on) m->gd.max_norm = max_norm;
+  return MD2_OK;
+}
+
+bool model_grad_guard_on(const Model* m) { return m && m->gd.on; }
+
+int model_grad_guard_state(Model* m, const md2_guard_state** dev) {
+  MD2_CHECK_ARG(m && dev, "grad_guard_state args");
+  if (!m->gd.state) {
+    set_error("grad_guard_state: the guard was never switched on (md2_model_set_grad_guard)");
+    return MD2_ESTATE;
+  }
+  *dev = m->gd.state;
+  return MD2_OK;
 }
 
 int model_adam_segment(Model* m, int k, float* adam_m, float* adam_v, float lr, float b1, float b2,
@@ -267,6 +323,11 @@ int model_adam_segment(Model* m, int k, float* adam_m, float* adam_v, float lr, 
   MD2_CHECK_ARG(m && adam_m && adam_v && step >= 1, "adam_segment args");
   MD2_CHECK_ARG(k >= 0 && k < 6, "segment index");
   MD2_TRY(refuse_testmode(m, "adam_segment"));
+  if (m->gd.on) {
+    set_error("adam_segment: the gradient guard is on -- a segment's update cannot know the global norm "
+              "(md2_model_adam takes the whole step)");
+    return MD2_ENOTSUP;
+  }
   const double bc1 = 1.0 - std::pow((double)b1, step), bc2 = 1.0 - std::pow((double)b2, step);
   return m->adam_segment(k, adam_m, adam_v, lr, b1, b2, eps, (float)bc1, (float)bc2, grad_scale, st);
 }

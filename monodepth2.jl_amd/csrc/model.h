@@ -120,6 +120,11 @@ int model_set_bn_stats(Model* m, const float* in, hipStream_t st);
 // folded into the convs; every training entry point returns MD2_ESTATE until it is switched off
 int model_set_testmode(Model* m, int on, hipStream_t st);
 int model_testmode(Model* m);
+// gradient guard (md2.h, md2_model_set_grad_guard): while on, model_adam and the captured step run
+// grad_norm over the flat gradient and the guarded ADAM; model_adam_segment refuses
+int model_set_grad_guard(Model* m, int on, float max_norm);
+bool model_grad_guard_on(const Model* m);
+int model_grad_guard_state(Model* m, const md2_guard_state** dev);
 float* model_grads(Model* m);          // the caller-owned flat gradient vector
 size_t model_device_bytes(Model* m);
 

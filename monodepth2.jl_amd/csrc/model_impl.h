@@ -206,7 +206,19 @@ struct StepGraph {
   float lr = 0.f;
   int with_auto = -1;
   int with_net = -1;   // a separate network input (train_step_graph_aug) is part of the capture
+  int guard_on = -1;   // the gradient guard and its max_norm are part of the capture too
+  float guard_max = 0.f;
   int next_step = -1;
+};
+
+// Gradient guard (md2_model_set_grad_guard): between the backward and ADAM, grad_norm over the whole
+// flat gradient writes `state`, which the guarded ADAM reads.  Both buffers are allocated at the
+// first switch-on and kept.
+struct GradGuard {
+  bool on = false;
+  float max_norm = 0.f;
+  md2_guard_state* state = nullptr;
+  void* ws = nullptr;
 };
 
 class Model {
@@ -308,6 +320,7 @@ class Model {
   Profiler pf;
   TestMode tm;
   StepGraph g;
+  GradGuard gd;
 
   // ---- step state
   const float* cur_x = nullptr;

@@ -173,4 +173,15 @@ int adam_step_dev(float* p, const float* g, float* m, float* v, long n, float lr
 int adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
               float eps, float bc1, float bc2, float gscale, hipStream_t st);
 
+// ---- guarded step (md2.h, md2_grad_norm): grad_guard.hip writes the state, these read it ----
+size_t grad_norm_workspace_bytes(long long n);   // 0 for n outside 1..2^31
+// the two launches; arguments validated by the caller
+int grad_norm(const float* g, long long n, float grad_scale, float max_norm, md2_guard_state* state,
+              void* workspace, hipStream_t st);
+// adam_step / adam_step_dev with gscale and the verdict read from *gs
+int adam_step_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
+                      float eps, float bc1, float bc2, const md2_guard_state* gs, hipStream_t st);
+int adam_step_dev_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
+                          float eps, const float* bc, const md2_guard_state* gs, hipStream_t st);
+
 }  // namespace md2

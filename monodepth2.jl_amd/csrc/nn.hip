@@ -1902,6 +1902,60 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
   p[i] -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
 }
 
+// The guarded forms (md2_adam_guarded, md2_model_set_grad_guard): the gradient scale and the verdict
+// come from the device state grad_guard_finish wrote (grad_guard.hip).  A step that is not ok
+// returns before it touches p, m or v; otherwise the expressions are those of the kernels above, in
+// this translation unit so that they are compiled alike.
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, long n,
+                                                           float lr, float b1, float b2, float eps, float bc1,
+                                                           float bc2, const md2_guard_state* __restrict__ gs) {
+  if (!gs->ok) return;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float gscale = gs->gscale;
+  const float gi = g[i] * gscale;
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  p[i] -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+}
+
+__global__ __launch_bounds__(256) void adam_dev_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               long n, float lr, float b1, float b2, float eps,
+                                                               const float* __restrict__ bc,
+                                                               const md2_guard_state* __restrict__ gs) {
+  if (!gs->ok) return;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float bc1 = bc[0], bc2 = bc[1];
+  const float gscale = gs->gscale;
+  const float gi = g[i] * gscale;
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  p[i] -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+}
+
+int adam_step_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
+                      float eps, float bc1, float bc2, const md2_guard_state* gs, hipStream_t st) {
+  hipLaunchKernelGGL(adam_guarded_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2,
+                     eps, bc1, bc2, gs);
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
+int adam_step_dev_guarded(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2,
+                          float eps, const float* bc, const md2_guard_state* gs, hipStream_t st) {
+  hipLaunchKernelGGL(adam_dev_guarded_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, p, g, m, v, n, lr, b1,
+                     b2, eps, bc, gs);
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
 int adam_prep(int* step, float* bc, float b1, float b2, hipStream_t st) {
   hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, st, step, bc, b1, b2);
   MD2_LAUNCH_CHECK();

@@ -7,8 +7,8 @@ op runs the HIP kernels and a missing library raises."""
 from ._lib import MD2Error, lib  # noqa: F401
 from .loss import Params, TrainCache, depth10k_intrinsics, loss_tail, pack_poses  # noqa: F401
 from .model import (ADAM, DepthDecoder, Model, Pose, PoseDecoder, ResidualNetwork, ResNet,  # noqa: F401
-                    disparity_bins, eval_disparity, eval_pose, flux_params, gradient, param_table, pullback, set_flux_params,
-                    train_loss, train_step)
+                    decode_guard_state, disparity_bins, eval_disparity, eval_pose, flux_params, grad_norm, gradient, param_table,
+                    pullback, set_flux_params, train_loss, train_step)
 from .slow_depth import SlowDepth, adam_update, slow_depth  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .data import (DataLoader, DChain, Depth10k, FlipX, KittyDataset, find_static, load_kitti_poses,  # noqa: F401
@@ -32,4 +32,5 @@ __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_pos
            "post_process_disparity",
            "JITTER_DTYPE", "ColorJitter", "color_jitter", "jitter_params",
            "eval_pose", "pose_errors", "evaluate_pose", "pose_windows", "chord_to_degrees",
-           "load_kitti_poses", "relative_poses"]
+           "load_kitti_poses", "relative_poses",
+           "grad_norm", "decode_guard_state"]

@@ -103,6 +103,14 @@ class Jitter(C.Structure):
 POSE_EVAL_MAX_SEQ = 64   # include/md2.h MD2_POSE_EVAL_MAX_SEQ
 POSE_EVAL_MAX_TRACK = 16  # include/md2.h MD2_POSE_EVAL_MAX_TRACK
 
+
+
+class GuardState(C.Structure):
+    """``md2_guard_state`` (40 bytes)."""
+    _fields_ = [("sumsq", C.c_double), ("nonfinite", C.c_longlong), ("skipped", C.c_longlong),
+                ("norm", C.c_float), ("coef", C.c_float), ("gscale", C.c_float), ("ok", C.c_int)]
+
+
 _lib = None
 _load_error = None
 
@@ -191,6 +199,12 @@ _SIGS = {
     "md2_model_eval_pose": (C.c_int, [P, P, C.c_int, C.POINTER(C.c_void_p), P]),
     "md2_pose_eval_workspace_size": (C.c_size_t, [C.c_longlong]),
     "md2_pose_eval": (C.c_int, [P, P, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, P, P, P, P, P, P]),
+    "md2_grad_norm_workspace_size": (C.c_size_t, [C.c_longlong]),
+    "md2_grad_norm": (C.c_int, [P, C.c_longlong, C.c_float, C.c_float, P, P, P]),
+    "md2_adam_guarded": (C.c_int, [P, P, P, P, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    C.c_int, P, P]),
+    "md2_model_set_grad_guard": (C.c_int, [P, C.c_int, C.c_float]),
+    "md2_model_grad_guard_state": (C.c_int, [P, C.POINTER(C.c_void_p)]),
     "md2_model_debug_tensor": (C.c_int, [P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int)]),
     "md2_model_features": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -84,12 +84,15 @@ class GradAllReduce:
 
 def train_step(executor, model, opt, x, comm: Optional[GradAllReduce] = None, loss=None):
     """forward_loss -> backward segments (each followed by its bucket all-reduce) -> ADAM with
-    gradient scale 1/world.  Returns the device loss tensor (this rank's shard loss)."""
+    gradient scale 1/world.  Returns the device loss tensor (this rank's shard loss).  A guarded
+    ``opt`` (``ADAM(max_grad_norm=..., skip_nonfinite=...)``) measures, clips and skips on the reduced
+    gradient, after the last bucket: every rank sees the same gradient and takes the same decision."""
     comm = comm or GradAllReduce()
     out = executor.forward_loss(x, None, loss=loss)
     # one update after the last bucket unless MD2_SEG_UPDATE=1 (concurrent per-segment updates
     # measured 2% slower at N=1, profiles/r04_seg_update_ab.txt)
-    if comm.active or os.environ.get("MD2_SEG_UPDATE") != "1":
+    # (and with a guarded optimiser: the gradient guard needs the whole reduced gradient)
+    if comm.active or os.environ.get("MD2_SEG_UPDATE") != "1" or opt.guarded:
         for k in range(executor.nseg):
             off, ln = executor.backward_segment(k)
             comm.bucket_ready(model.grad, off, ln)

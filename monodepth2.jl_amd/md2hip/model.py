@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import ModelCfg, check, lib, ptr, stream_of
+from ._lib import GuardState, ModelCfg, check, lib, ptr, stream_of
 from .loss import Params, TrainCache, depth10k_intrinsics, loss_tail
 
 
@@ -143,6 +143,8 @@ def flux_init(table, total, seed=42):
 class _Executor:
     """One libmd2hip model instance (activations/workspace) for a fixed problem size."""
 
+    _guard = (False, None)                  # the library's gradient-guard (on, max_norm) of this executor
+
     def __init__(self, model: "Model", batch, height, width, cache: TrainCache, params: Params,
                  num_bins: int = 32):
         self.model = model
@@ -163,6 +165,27 @@ class _Executor:
         self.bn_version = 0                 # Model.bn_version its running statistics reflect (0: 0 / 1)
         self.testmode = False
         self.sync()
+
+    def set_grad_guard(self, on: bool, max_norm: float = float("inf")):
+        """Switch the gradient guard of this executor (md2_model_set_grad_guard): while on, every
+        update through it measures the global gradient norm, clips by ``max_norm`` (inf: no clipping)
+        and skips the update when a gradient entry is not finite.  A change clears ``skipped`` and
+        synchronises the device; an unchanged setting is not sent again."""
+        want = (True, float(max_norm)) if on else (False, None)
+        if want == self._guard:
+            return
+        check(lib().md2_model_set_grad_guard(self.handle, int(on), float(max_norm) if on else 0.0),
+              "md2_model_set_grad_guard")
+        self._guard = want
+
+    def guard_tensor(self):
+        """The executor's ``md2_guard_state`` as a 40-byte uint8 device tensor: a copy enqueued on
+        the current stream (no synchronisation), holding the state after the steps enqueued so far.
+        ``md2hip.decode_guard_state`` reads it on the host."""
+        import torch
+        p = C.c_void_p()
+        check(lib().md2_model_grad_guard_state(self.handle, C.byref(p)), "md2_model_grad_guard_state")
+        return _wrap(p.value, (C.sizeof(GuardState),), self.model.device, torch.uint8)
 
     def sync(self):
         """Bring this executor up to the model: re-pack its conv weights if the flat parameters
@@ -318,6 +341,7 @@ class _Executor:
             opt.m = torch.zeros_like(self.model.flat)
             opt.v = torch.zeros_like(self.model.flat)
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
+        opt._apply_guard(self)
         opt.t += 1
         if x_net is None:
             check(lib().md2_model_train_step_graph(self.handle, ptr(x), ptr(am), ptr(opt.m), ptr(opt.v), opt.eta,
@@ -651,13 +675,84 @@ def flux_params(model: Model, grads: bool = False):
     return out
 
 
-class ADAM:
-    """Flux ``ADAM(eta, (beta1, beta2))`` with eps = 1e-8 (scripts/script.jl:85)."""
+def decode_guard_state(state):
+    """The fields of an ``md2_guard_state`` held in a 40-byte uint8 tensor (``grad_norm``,
+    ``ADAM.guard_tensor``) as a dict: sumsq, nonfinite, skipped, norm, coef, gscale, ok.  Copies to
+    the host, which SYNCHRONISES for a device tensor."""
+    raw = bytes(state.detach().cpu().numpy().tobytes())
+    if len(raw) != C.sizeof(GuardState):
+        raise ValueError(f"a guard state is {C.sizeof(GuardState)} bytes")
+    s = GuardState.from_buffer_copy(raw)
+    return {"sumsq": s.sumsq, "nonfinite": int(s.nonfinite), "skipped": int(s.skipped), "norm": s.norm,
+            "coef": s.coef, "gscale": s.gscale, "ok": bool(s.ok)}
 
-    def __init__(self, eta=1e-3, beta=(0.9, 0.999), eps=1e-8):
+
+def grad_norm(g, grad_scale: float = 1.0, max_norm: float = math.inf, state=None, workspace=None):
+    """``md2_grad_norm`` on any float32 device tensor (read flat, in memory order): the global L2
+    norm of ``grad_scale * g``, the coefficient that clips it to ``max_norm`` and the count of
+    non-finite entries, written on the device into ``state`` -- returned as a 40-byte uint8 tensor
+    (``decode_guard_state``; ``md2_adam_guarded`` reads it in place).  Pass the same ``state`` again to
+    accumulate ``skipped``; a fresh one starts at zero.  ``workspace``: a uint8 tensor of at least
+    ``md2_grad_norm_workspace_size(g.numel())`` bytes (allocated when None).  Two launches on the
+    current stream, bitwise reproducible, no synchronisation."""
+    import torch
+    if g.dtype != torch.float32 or g.device.type != "cuda" or not g.is_contiguous() or g.numel() < 1:
+        raise ValueError("g must be a non-empty contiguous float32 CUDA tensor")
+    n = g.numel()
+    need = lib().md2_grad_norm_workspace_size(n)
+    if state is None:
+        state = torch.zeros(C.sizeof(GuardState), dtype=torch.uint8, device=g.device)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
+    if state.dtype != torch.uint8 or state.numel() != C.sizeof(GuardState) or state.device != g.device:
+        raise ValueError("state must be a 40-byte uint8 tensor on g's device")
+    if workspace.device != g.device or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"workspace must hold {need} bytes on g's device")
+    check(lib().md2_grad_norm(ptr(g), n, float(grad_scale), float(max_norm), ptr(state), ptr(workspace),
+                              stream_of(g.device)), "md2_grad_norm")
+    return state
+
+
+class ADAM:
+    """Flux ``ADAM(eta, (beta1, beta2))`` with eps = 1e-8 (scripts/script.jl:85).
+
+    ``max_grad_norm`` (clip the global L2 norm of the gradient to it) and ``skip_nonfinite`` (leave
+    the parameters and the moments alone when a gradient entry is NaN or Inf) switch the library's
+    gradient guard on (md2_model_set_grad_guard): either option measures the norm and skips a
+    non-finite step, ``skip_nonfinite`` alone clips nothing.  A skipped step still counts in ``t``.
+    Everything runs on the device; only ``guard_state()`` synchronises."""
+
+    def __init__(self, eta=1e-3, beta=(0.9, 0.999), eps=1e-8, max_grad_norm=None, skip_nonfinite=False):
         self.eta, self.beta, self.eps = eta, beta, eps
         self.t = 0
         self.m = self.v = None
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard_ex = None               # the executor whose state the last guarded step wrote
+
+    @property
+    def guarded(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _apply_guard(self, ex):
+        """Bring ``ex``'s gradient guard to this optimiser's options (a no-op when they match)."""
+        ex.set_grad_guard(self.guarded, self.max_grad_norm if self.max_grad_norm is not None else math.inf)
+        if self.guarded:
+            self._guard_ex = ex
+
+    def guard_tensor(self):
+        """The guard's device state after the steps enqueued so far, as 40 bytes (uint8) on the
+        device -- no synchronisation; ``md2hip.decode_guard_state`` reads it."""
+        if self._guard_ex is None:
+            raise RuntimeError("guard_state needs a guarded step (max_grad_norm / skip_nonfinite) first")
+        return self._guard_ex.guard_tensor()
+
+    def guard_state(self):
+        """``{norm, coef, ok, skipped, nonfinite}`` of the last guarded step.  SYNCHRONISES."""
+        s = decode_guard_state(self.guard_tensor())
+        return {k: s[k] for k in ("norm", "coef", "ok", "skipped", "nonfinite")}
 
     def update(self, model: Model, grad_scale: float = 1.0):
         """``Flux.Optimise.update!(opt, θ, ∇)`` on the flat vector (in place)."""
@@ -670,6 +765,7 @@ class ADAM:
         ex = model._last
         if ex is None:
             raise RuntimeError("ADAM.update needs a preceding train_loss/gradient")
+        self._apply_guard(ex)
         # md2_model_adam updates flat (shared by every executor) and re-packs ex's weights only
         check(lib().md2_model_adam(ex.handle, ptr(self.m), ptr(self.v), self.eta, self.beta[0],
                                    self.beta[1], self.eps, self.t, grad_scale, stream_of(model.device)),
@@ -688,6 +784,7 @@ class ADAM:
         ex = model._last
         if ex is None:
             raise RuntimeError("ADAM.update_segment needs a preceding train_loss/gradient")
+        self._apply_guard(ex)               # guarded: the library refuses (MD2_ENOTSUP), use update()
         if k == 0:
             self.t += 1
         check(lib().md2_model_adam_segment(ex.handle, k, ptr(self.m), ptr(self.v), self.eta, self.beta[0],
