@@ -1,6 +1,6 @@
 // md2_grad_norm: the global L2 norm of a flat fp32 gradient, the clip coefficient and the
 // non-finite count, as one device state block (md2_guard_state) that the guarded ADAM kernels
-// (nn.hip) read.  include/md2.h states the summation order and every operation of the finish.
+// (optim.hip) read. include/md2.h states the summation order and every operation of the finish.
 //
 // Built with -ffp-contract=off and correctly rounded division / square root: the finish is a handful
 // of scalar operations that the NumPy restatement of the tests repeats bit for bit.  (The sum itself

@@ -74,21 +74,21 @@ int Model::conv_d_bn(RConv& c, int nimg, const float* dy, float* da, long da_bs,
     prof_conv(e, c, s, "dgrad", st);
     return bn_bwd(bn, da, nullptr, y, nimg, HW, dyprev, nullptr, 0, st, true);
   }
+  BNBwd b = bn_bwd_desc(bn, y, dyprev, true);
+  b.slabs = SlabIn{d.slab, d.splits};
   if (sw.fuse_bn_bwd && bn_channel_fits(nimg, HW)) {
     // the slabs are summed in the block's registers: DA (read by this backward alone) is not written
-    MD2_TRY(bn_bwd_channel(nullptr, SlabIn{d.slab, d.splits}, nullptr, y, bn.mean, bn.invstd,
-                           P(bn.p.g), P(bn.p.b), Gd(bn.p.g), Gd(bn.p.b), nimg, bn.p.c, HW, dyprev,
-                           nullptr, 0, st));
+    MD2_TRY(bn_bwd_channel(b, nimg, bn.p.c, HW, st));
     prof_conv(e, c, s, "dgrad", st);
     return MD2_OK;
   }
   BNStatsWs w = bnws;
   w.parts = bn_parts(bn.p.c, nimg, HW);
-  MD2_TRY(bn_bwd_partial_slabs(SlabIn{d.slab, d.splits}, da, y, bn.mean, bn.invstd, nimg, bn.p.c,
-                               HW, w, st, P(bn.p.g), P(bn.p.b)));
+  MD2_TRY(bn_bwd_partial_slabs(b, da, nimg, bn.p.c, HW, w, st));
   prof_conv(e, c, s, "dgrad", st);
-  return bn_bwd_apply_fused(da, nullptr, y, bn.mean, bn.invstd, P(bn.p.g), w, Gd(bn.p.g),
-                            Gd(bn.p.b), nimg, bn.p.c, HW, dyprev, nullptr, 0, st, P(bn.p.b));
+  b.slabs = SlabIn{};
+  b.dout = da;
+  return bn_bwd_apply_fused(b, nimg, bn.p.c, HW, w, st);
 }
 
 int Model::act_bias(const float* out, const float* dout, float* dpre, int nimg, int C, long HW, int act,
@@ -104,22 +104,37 @@ int Model::act_bias(const float* out, const float* dout, float* dpre, int nimg, 
   return MD2_OK;
 }
 
-// mask: the BN+ReLU output whose ReLU gates dout, or nullptr with relu_from_y for a residual-free
-// BN+ReLU (stem, intra-block): the mask is re-derived from y (bit-exact, one read less)
+// the operands every backward of `bn` shares; relu_from_y: a residual-free BN+ReLU (stem,
+// intra-block), whose ReLU mask is re-derived from y (bit-exact, one read less)
+BNBwd Model::bn_bwd_desc(RBN& bn, const float* y, float* dy, bool relu_from_y) {
+  BNBwd b;
+  b.y = y;
+  b.mean = bn.mean;
+  b.invstd = bn.invstd;
+  b.gamma = P(bn.p.g);
+  b.mbeta = relu_from_y ? P(bn.p.b) : nullptr;
+  b.dgamma = Gd(bn.p.g);
+  b.dbeta = Gd(bn.p.b);
+  b.dy = dy;
+  return b;
+}
+
+// mask: the BN+ReLU output whose ReLU gates dout (ignored with relu_from_y)
 int Model::bn_bwd(RBN& bn, const float* dout, const float* mask, const float* y, int nimg, long HW, float* dy,
                   float* dres, int dres_acc, hipStream_t st, bool relu_from_y, SkipAdd sk, int slot) {
   BNStatsWs w = bnws;
   w.partials += slot * bn_slot;
   w.parts = bn_parts(bn.p.c, nimg, HW);
-  const float* mg = relu_from_y ? P(bn.p.g) : nullptr;
-  const float* mb = relu_from_y ? P(bn.p.b) : nullptr;
-  if (relu_from_y) mask = nullptr;
+  BNBwd b = bn_bwd_desc(bn, y, dy, relu_from_y);
+  b.dout = dout;
+  b.mask = relu_from_y ? nullptr : mask;
+  b.dres = dres;
+  b.dres_accumulate = dres_acc;
+  b.skip = sk;
   if (sw.fuse_bn_bwd && bn_channel_fits(nimg, HW))   // layers 3-4 at the bench shape: one launch
-    return bn_bwd_channel(dout, SlabIn{}, mask, y, bn.mean, bn.invstd, P(bn.p.g), mb, Gd(bn.p.g),
-                          Gd(bn.p.b), nimg, bn.p.c, HW, dy, dres, dres_acc, st, sk);
-  MD2_TRY(bn_bwd_partial(dout, mask, y, bn.mean, bn.invstd, nimg, bn.p.c, HW, w, st, mg, mb, sk));
-  return bn_bwd_apply_fused(dout, mask, y, bn.mean, bn.invstd, P(bn.p.g), w, Gd(bn.p.g),
-                            Gd(bn.p.b), nimg, bn.p.c, HW, dy, dres, dres_acc, st, mb, sk);
+    return bn_bwd_channel(b, nimg, bn.p.c, HW, st);
+  MD2_TRY(bn_bwd_partial(b, nimg, bn.p.c, HW, w, st));
+  return bn_bwd_apply_fused(b, nimg, bn.p.c, HW, w, st);
 }
 
 // the decoder skip gradient d_skip[si] on the target slice of encoder feature si (si = 1..3, the

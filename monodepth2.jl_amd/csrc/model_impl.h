@@ -392,6 +392,7 @@ class Model {
                 long HW, float* dyprev, hipStream_t st);
   int act_bias(const float* out, const float* dout, float* dpre, int nimg, int C, long HW, int act,
                hipStream_t st, float* bp_buf = nullptr);
+  BNBwd bn_bwd_desc(RBN& bn, const float* y, float* dy, bool relu_from_y);
   int bn_bwd(RBN& bn, const float* dout, const float* mask, const float* y, int nimg, long HW, float* dy,
              float* dres, int dres_acc, hipStream_t st, bool relu_from_y = false, SkipAdd sk = SkipAdd{},
              int slot = 0);

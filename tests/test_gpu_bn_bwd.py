@@ -1,4 +1,4 @@
-"""GPU: the one-kernel BatchNorm backward (bn_bwd_channel in nn.hip: a channel that fits in one
+"""GPU: the one-kernel BatchNorm backward (bn_bwd_channel in bn_bwd.hip: a channel that fits in one
 block is summed and applied from registers, MD2_FUSE_BN_BWD) against the two-pass path it replaces
 (bn_bwd_partial + bn_bwd_apply_fused, MD2_FUSE_BN_BWD=0).  Both take the same fp64 sums of the same
 values, in another order, so dgamma / dbeta / dy agree to the last bits and not bitwise -- the

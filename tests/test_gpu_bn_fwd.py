@@ -1,4 +1,4 @@
-"""GPU: the one-kernel BatchNorm forward (bn_fwd_channel in nn.hip: a channel that fits in one
+"""GPU: the one-kernel BatchNorm forward (bn_fwd_channel in bn_fwd.hip: a channel that fits in one
 block is summed and applied from registers, MD2_FUSE_BN_FWD) against the two passes it replaces
 (bn_stats_partial[_slabs] + bn_apply_fused, MD2_FUSE_BN_FWD=0).  Both take the same fp64 sums of
 the same values, in another order, and finalise them with the same device code, so mean / invstd
