@@ -592,6 +592,14 @@ HeadW conv_head_w(const ConvShape& s, int mode, const float* packed) {
   return w;
 }
 HeadIn conv_head_in(const TensorIn& x) { return HeadIn{x.p0, x.bs0, x.bdiv, x.bhi}; }
+HeadJob conv_head_job(const ConvShape& s) {
+  HeadJob j{};
+  j.Cin = s.Cin;
+  j.H = s.H;
+  j.W = s.W;
+  j.N = s.N;
+  return j;
+}
 
 // the 16-row kernel (conv_px16.inc) runs tap-major 3x3 / stride-1 fwd (Cout <= 16, not a Cout = 1
 // head) and dgrad (Cin <= 16); MD2_PX16=0 falls back to the 32-row tiles
@@ -650,7 +658,13 @@ static size_t wgrad_ws_bytes(const ConvShape& s, int c0) {
 
 // the split count depends on the concat split only through CW: size for every possible CW
 size_t conv_wgrad_workspace(const ConvShape& s) {
-  if (head_path(s)) return head_wgrad_workspace(s);
+  if (head_path(s)) {   // the route is known only at the call (alignment, accumulate): the larger need
+    float sized;        // a filter gradient is asked for; never written
+    HeadJob j = conv_head_job(s);
+    j.dw = &sized;
+    const size_t batched = s.reflect && !heads_job_unfit(j) ? heads_bwd_workspace(&j, 1) : 0;
+    return std::max(head_wgrad_workspace(j), batched);
+  }
   size_t b = wgrad_ws_bytes(s, s.Cin);
   for (int c0 = 16; c0 <= 128; c0 *= 2) b = std::max(b, wgrad_ws_bytes(s, c0));
   return b;

@@ -119,7 +119,13 @@ int conv_dgrad(const ConvShape& s, const float* dy, const float* wpacked_d, cons
   if (head_path(s) && dx.c0 >= s.Cin) {
     MD2_CHECK_ARG(!conv_px2_used(s, 1) && !conv_tap_major(s, 1), "head: packed layout");
     conv_arith_ref() = 0;
-    return head_dgrad(s, dy, conv_head_w(s, 1, wpacked_d), dx.p0, dx.bs0, dx.accumulate, st);
+    HeadJob j = conv_head_job(s);
+    j.wd = conv_head_w(s, 1, wpacked_d);
+    j.dy = dy;
+    j.dx = dx.p0;
+    j.dxbs = dx.bs0;
+    if (s.reflect && !dx.accumulate && !heads_job_unfit(j)) return heads_bwd(&j, 1, nullptr, 0, st);
+    return head_dgrad(j, s.reflect, dx.accumulate, st);
   }
   ConvArgs a{};
   fill_common(a, s);

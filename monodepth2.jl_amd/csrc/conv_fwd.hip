@@ -19,8 +19,14 @@ int conv_fwd(const ConvShape& s, const TensorIn& x, const float* wpacked, const 
   if (head_path(s) && x.c0 >= s.Cin && y.c0 >= 1) {
     MD2_CHECK_ARG(!conv_px2_used(s, 0), "head: packed layout");
     conv_arith_ref() = 0;
-    return head_fwd(s, conv_head_in(x), conv_head_w(s, 0, wpacked), y.bias, y.act, y.p0, y.bs0,
-                    y.accumulate, st);
+    HeadJob j = conv_head_job(s);
+    j.x = conv_head_in(x);
+    j.wf = conv_head_w(s, 0, wpacked);
+    j.bias = y.bias;
+    j.y = y.p0;
+    j.ybs = y.bs0;
+    if (s.reflect && !y.accumulate && !heads_job_unfit(j)) return heads_fwd(&j, 1, y.act, st);
+    return head_fwd(j, s.reflect, y.act, y.accumulate, st);
   }
   ConvArgs a{};
   fill_common(a, s);

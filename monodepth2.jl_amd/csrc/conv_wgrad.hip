@@ -85,7 +85,13 @@ int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw
   MD2_CHECK_ARG(x.c0 >= s.Cin || x.p1 != nullptr, "conv_wgrad: second input tensor missing");
   if (head_path(s) && x.c0 >= s.Cin) {
     conv_arith_ref() = 0;
-    return head_wgrad(s, conv_head_in(x), dy, dw, db, accumulate, ws.ptr, ws.bytes, st);
+    HeadJob j = conv_head_job(s);
+    j.x = conv_head_in(x);
+    j.dy = dy;
+    j.dw = dw;
+    j.db = db;
+    if (s.reflect && !accumulate && !heads_job_unfit(j)) return heads_bwd(&j, 1, ws.ptr, ws.bytes, st);
+    return head_wgrad(j, s.reflect, accumulate, ws.ptr, ws.bytes, st);
   }
   const WPlan p = plan_wgrad(s, x.c0);
   const bool tap = p.cw > 0;

@@ -74,22 +74,30 @@ CASES = [
     ((1, 16, 3, 5), 12, 3, 1, 1, True, "elu", True),             # K < one 64-pixel chunk
     ((3, 32, 10, 30), 20, 3, 1, 1, False, "relu", True),         # Cout 20: ragged second row tile
     ((12, 96, 64, 208), 32, 3, 1, 1, True, "elu", True),         # decoder level-4 conv2 at bench size
-    # Cout = 1 heads (VALU kernels of head.hip): reflect folds on 2/3-wide maps, zero padding,
-    # ragged and > 8-channel groups, the bench-size full-resolution head
-    ((2, 16, 2, 2), 1, 3, 1, 1, True, "sigmoid", True),          # every pixel folds twice
-    ((2, 8, 3, 3), 1, 3, 1, 1, True, "sigmoid", True),           # q = 1 = n-2 folds both ways
-    ((3, 5, 7, 11), 1, 3, 1, 1, True, "sigmoid", True),          # ragged channel group
-    ((2, 13, 6, 9), 1, 3, 1, 1, False, None, True),              # zero padding, no act
-    ((2, 32, 16, 52), 1, 3, 1, 1, True, "sigmoid", True),        # head4 geometry
-    ((2, 128, 4, 13), 1, 3, 1, 1, True, "sigmoid", True),        # head2 (16 channel groups)
-    ((12, 16, 128, 416), 1, 3, 1, 1, True, "sigmoid", True),     # head5 at bench size
-    # column-strip head kernels (W >= 64): ragged segments / bands / channel blocks, zero padding,
-    # both row folds inside one strip, the head3 geometry
-    ((2, 37, 13, 70), 1, 3, 1, 1, True, "sigmoid", True),
-    ((2, 7, 9, 66), 1, 3, 1, 1, False, None, True),
-    ((4, 8, 130, 256), 1, 3, 1, 1, False, None, True),           # zero padding, strip fwd/wgrad
-    ((1, 16, 4, 64), 1, 3, 1, 1, True, "sigmoid", True),
-    ((2, 64, 32, 104), 1, 3, 1, 1, True, "sigmoid", True),
+    # Cout = 1 heads (head.hip), two routes.  Reflect-padded maps with H >= 2 and an even W >= 4
+    # reach the batched pixel-vector kernels the model runs (heads_fwd / heads_bwd as one job):
+    # marked [batched] here, (2, 16, 32, 64) above, and head2 / head3 / head4 of the bench step below.
+    # Zero padding and odd or 2-wide maps reach the pixel-per-lane fallback: marked [fallback].
+    ((2, 16, 2, 2), 1, 3, 1, 1, True, "sigmoid", True),          # [fallback] every pixel folds twice
+    ((2, 8, 3, 3), 1, 3, 1, 1, True, "sigmoid", True),           # [fallback] q = 1 = n-2 folds both ways
+    ((3, 5, 7, 11), 1, 3, 1, 1, True, "sigmoid", True),          # [fallback] ragged channel group
+    ((2, 13, 6, 9), 1, 3, 1, 1, False, None, True),              # [fallback] zero padding, no act
+    ((2, 32, 16, 52), 1, 3, 1, 1, True, "sigmoid", True),        # [batched] head4 geometry
+    ((2, 128, 4, 13), 1, 3, 1, 1, True, "sigmoid", True),        # [fallback] odd W: head2 (16 channel groups)
+    ((12, 16, 128, 416), 1, 3, 1, 1, True, "sigmoid", True),     # [batched] head5 at bench size
+    # wide maps (W >= 64): W % 4 == 2, a ragged channel quarter, both row folds in a 4-row map, the
+    # head3 geometry on the batched kernels; wide zero-padded maps on the fallback
+    ((2, 37, 13, 70), 1, 3, 1, 1, True, "sigmoid", True),        # [batched] float2 vectors
+    ((2, 7, 9, 66), 1, 3, 1, 1, False, None, True),              # [fallback] zero padding
+    ((4, 8, 130, 256), 1, 3, 1, 1, False, None, True),           # [fallback] zero padding, many partial blocks
+    ((1, 16, 4, 64), 1, 3, 1, 1, True, "sigmoid", True),         # [batched]
+    ((2, 64, 32, 104), 1, 3, 1, 1, True, "sigmoid", True),       # [batched]
+    # edges of the batched kernels at the smallest shape that shows each (all [batched])
+    ((2, 5, 2, 4), 1, 3, 1, 1, True, "sigmoid", True),           # every row folds; one vector per row; odd Cin
+    ((3, 3, 3, 6), 1, 3, 1, 1, True, "sigmoid", True),           # float2 vectors; row 1 folds both ways; Cin < 4
+    ((1, 18, 5, 12), 1, 3, 1, 1, True, "sigmoid", True),         # a second, ragged data-gradient chunk
+    ((1, 2, 4, 4), 1, 3, 1, 1, True, "sigmoid", True),           # 4 vectors: almost every lane a non-owner
+    ((2, 4, 63, 256), 1, 3, 1, 1, True, "sigmoid", True),        # 131 tiles: runs of 8, a ragged run and tile
     # LDS-halo kernel (conv_halo.inc) edges: a 256-pixel tile spanning many small images (W = 7:
     # 40 halo rows), ragged N, C = 32 (two channel chunks, split-K of one), M = 128 (two row
     # tiles), a map too wide for the halo image (W = 200: conv_px3 instead)

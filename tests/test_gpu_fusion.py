@@ -104,14 +104,13 @@ np.save(out, m.flat.cpu().numpy())
 
 # settings every one of which an A/B sweep has run before (tools/*_sweep.sh, tools/ab_*.sh)
 KNOBS = {"MD2_PX_TARGET": "1024", "MD2_W_TILE": "2", "MD2_W_TARGET": "1024", "MD2_PX_V2": "0",
-         "MD2_HEAD_STRIP": "0", "MD2_UP_TILED": "0", "MD2_PHOTO_WAVES": "1024", "MD2_W16": "0",
-         "MD2_PX16": "0"}
+         "MD2_UP_TILED": "0", "MD2_PHOTO_WAVES": "1024", "MD2_W16": "0", "MD2_PX16": "0"}
 
 
 @pytest.mark.timeout(240)
 def test_tuning_knobs_ignored_without_md2_tuning(tmp_path):
     """The kernel / planner tuning knobs (common.h tuning_knob) change nothing unless MD2_TUNING=1:
-    two steps with nine knobs set (and no MD2_TUNING) give bit-identical parameters to a clean
+    two steps with eight knobs set (and no MD2_TUNING) give bit-identical parameters to a clean
     environment; with MD2_TUNING=1 the same knobs do take effect (other kernels, other roundings)."""
     import subprocess
     import sys

@@ -28,6 +28,7 @@ SH = [  # name, x_shape, cout, k, s, p, reflect
     ("h4", (12, 32, 64, 208), 1, 3, 1, 1, 1),
     ("h3", (12, 64, 32, 104), 1, 3, 1, 1, 1),
     ("h2", (12, 128, 16, 52), 1, 3, 1, 1, 1),
+    ("hz", (4, 8, 130, 256), 1, 3, 1, 1, 0),   # a wide zero-padded Cout = 1 map: the heads' fallback kernels
 ]
 _only = [a.split("=", 1)[1].split(",") for a in sys.argv if a.startswith("--only=")]
 if _only:

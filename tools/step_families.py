@@ -8,9 +8,11 @@ import sys
 
 FAMILIES = [
     ("conv 3x3/1x1/7x7 implicit GEMM (fwd/dgrad/wgrad)", r"conv_(px|px2|px3|px16|wgrad|wgrad_tap|wgrad16|wgrad_stem|wgrad_px3|halo3|whalo)_kernel|fold_reflect"),
+    # before the reductions, so that heads_wgrad_reduce_kernel counts with its family; \b keeps
+    # pose_head_* for the pose family
+    ("disparity heads (Cout=1)", r"\bheads?_"),
     ("split-K / wgrad reductions", r"(splitk_reduce|wgrad_reduce)"),
     ("BatchNorm (+ fused stem max pool)", r"bn_|maxpool"),
-    ("disparity heads (Cout=1)", r"head_"),
     ("photometric (warp+SSIM fwd+bwd)", r"photo_stream"),
     ("loss tail rest (smooth, means, adjoint, finalize, so3)", r"(smooth|disp_sum|up_adjoint|loss_|so3_|pose_grad_reduce)"),
     ("decoder upsample / activations", r"(upsample2|act_bias|act_backward|axpy|concat)"),
