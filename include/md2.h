@@ -196,12 +196,19 @@ int md2_warp_photometric_bwd(const md2_warp_cfg* cfg, const float* disp, const f
  * md2_load_kitti_u8      KittyDataset (src/kitty.jl:45-61): paths[3i+k] = frame k of sample i
  *                        (8-bit gray) -> out [n][3][1][h][w], each imresize'd to (h, w) and kept
  *                        N0f8 (md2hip/data.py imresize), then flipped if flip[i].
+ * md2_load_frames_native_u8   decode only, for md2_resize_frames: file i -> out + i * slot_bytes as
+ *                        decoded, rows of interleaved pixels [h][w][c] (no resize, no flip, no
+ *                        de-interleave), w[i] and h[i] its size.  c = 1 takes gray files, c = 3 RGB
+ *                        and RGBA files (the first three channels); any other file, and one with
+ *                        w * h * c > slot_bytes, is an error.
  * Host pointers; errors name the offending file. */
 int md2_png_info(const char* path, int* width, int* height, int* channels);
 int md2_load_triplets_u8(const char* const* paths, int n, int width, int height,
                          const unsigned char* flip, unsigned char* out, int threads);
 int md2_load_kitti_u8(const char* const* paths, int n, int height, int width,
                       const unsigned char* flip, unsigned char* out, int threads);
+int md2_load_frames_native_u8(const char* const* paths, int n, int c, unsigned char* out,
+                              long long slot_bytes, int* w, int* h, int threads);
 
 /* Data pipeline: N0f8 images -> Float32, out[i] = Float32(in[i]) / 255f0, the
  * `Float32.(channelview(x))` of src/dtk.jl:45 / src/kitty.jl:58 -- batches cross PCIe as bytes.
@@ -849,6 +856,81 @@ int md2_adam_guarded(float* p, const float* g, float* adam_m, float* adam_v, lon
                      const md2_guard_state* state /* device */, void* stream);
 int md2_model_set_grad_guard(md2_model* m, int on, float max_norm);
 int md2_model_grad_guard_state(md2_model* m, const md2_guard_state** dev);
+
+/* ------------------------------------------------------------------------------------------
+ * Frame resize on the device: m decoded images, each of its own size, resized to one target size
+ * and written as planes -- the step between a PNG decoder (md2_load_frames_native_u8) and the
+ * batch x[N][3][C][H][W] ([m] = [N*3] frames in order IS that layout).  Additive: MD2_ABI_VERSION
+ * is unchanged.
+ *
+ * Image i is src[offsets[i] ..], src_h[i] rows of src_w[i] interleaved pixels of c bytes, at any
+ * byte offset.  offsets, src_w, src_h and flip are HOST arrays, read before the call returns.
+ * All arithmetic is fp64, each operation rounded on its own (no fused multiply-add), until the
+ * final conversion.  The value of a source byte b is v = (double)b / 255.0.  For output pixel
+ * (y, x) of channel ch, with n_in / n_out the source / target length of an axis:
+ *
+ * MD2_RESIZE_IMRESIZE -- ImageTransformations' imresize as md2hip.data.imresize and
+ * md2_load_kitti_u8 restate it (bilinear, outer corners aligned, no antialiasing).  Per axis:
+ *  1. sf = (double)n_in / n_out;  p = sf * ((i + 1) - 0.5) + 0.5.
+ *  2. if sf < 1: p = min(max(p, 1), n_in).  p = p - 1.
+ *  3. i0 = min((int)floor(p), n_in - 1);  f = p - i0;  i1 = min(i0 + 1, n_in - 1).
+ * Then top = v(y0,x0) * (1 - fx) + v(y0,x1) * fx, bot the same on row y1, and
+ * r = top * (1 - fy) + bot * fy.
+ *
+ * MD2_RESIZE_ANTIALIAS -- the triangle filter widened by the reduction factor (Pillow's BILINEAR
+ * resize; torch's interpolate(mode="bilinear", antialias=True, align_corners=False)).  Per axis:
+ *  1. scale = (double)n_in / n_out;  fs = max(scale, 1);  center = (i + 0.5) * scale.
+ *  2. lo = max((int)((center - fs) + 0.5), 0);  hi = min((int)((center + fs) + 0.5), n_in); the
+ *     conversions truncate toward zero.
+ *  3. for k in [lo, hi): w_k = max(0, 1 - |((k - center) + 0.5) / fs|);  ww = the sum of the w_k,
+ *     k ascending, from 0.0;  the weight of tap k is w_k / ww.
+ * Then the horizontal sum of source row yy is H(yy) = sum over k of wx_k * v(yy, k), k ascending,
+ * from 0.0, each term a rounded product followed by a rounded add, and r = sum over yy of
+ * wy_yy * H(yy), yy ascending, from 0.0, in the same way.
+ *
+ * Both filters:
+ *  - an image that already has the target size is copied, r = v (what either formula gives);
+ *  - quantize = 1: q = rint(r * 255.0) (ties to even); out = (float)q / 255.0f, the bits
+ *    md2_unorm8_to_float gives for the byte q; out_u8 (may be NULL) = q.  This is the N0f8
+ *    rounding imresize applies; exact ties of r * 255 occur (a 2x reduction has the weights
+ *    1/8, 3/8, 3/8, 1/8), which is why the order of the sums is part of the interface;
+ *  - quantize = 0: out = (float)r; out_u8 must be NULL;
+ *  - flip[i] != 0 writes column x of the result at out_w - 1 - x (flip may be NULL: none).
+ * MD2_RESIZE_IMRESIZE with quantize = 1 gives the bytes of md2_load_kitti_u8.
+ *
+ * One launch for all images (the image index on a grid axis): a block owns 128 output columns
+ * and 8 output rows of one image, forms its tap weights once in LDS from the formulas above,
+ * stages the source rows it needs in LDS and streams them in ascending order -- a thread forms
+ * H(yy) for its column and adds wy * H(yy) into the rows of its band that yy belongs to, so no
+ * intermediate leaves the chip.  The staging loads are whole aligned 4-byte words: up to 3 bytes
+ * before the first and after the last byte of a source row are read (never past the word that
+ * holds a source byte) and ignored.  No workspace, no allocation, no copy, no atomics, no
+ * synchronisation with the host; the result is BITWISE REPRODUCIBLE; nothing beyond
+ * [m][c][out_h][out_w] of out and out_u8 is written.  The four host arrays ride in the kernel's
+ * argument block (1.1 KB at MD2_RESIZE_MAX_IMAGES: the reason for the cap; callers chunk).
+ * MD2_EINVAL (checked before any HIP call): a null cfg, src, offsets, src_w, src_h or out; m
+ * outside 1..MD2_RESIZE_MAX_IMAGES; c not 1 or 3; out_h, out_w, a src_w[i] or a src_h[i] outside
+ * 1..8192; an unknown filter; quantize not 0 or 1; out_u8 without quantize; a negative offset;
+ * out not 16-byte aligned; src_w[i] > 16 * out_w or src_h[i] > 16 * out_h (either filter: at
+ * most 33 taps per axis).
+ * ---------------------------------------------------------------------------------------- */
+#define MD2_RESIZE_MAX_IMAGES 64
+enum { MD2_RESIZE_IMRESIZE = 0, MD2_RESIZE_ANTIALIAS = 1 };
+typedef struct md2_resize_cfg {
+  int m;             /* images in this call, 1..MD2_RESIZE_MAX_IMAGES                     */
+  int c;             /* 1 or 3; a source image is [h][w][c] bytes, interleaved, as decoded */
+  int out_h, out_w;  /* target size, 1..8192                                              */
+  int filter;        /* MD2_RESIZE_IMRESIZE | MD2_RESIZE_ANTIALIAS                        */
+  int quantize;      /* 1: round the result to N0f8 (the element type imresize keeps)     */
+} md2_resize_cfg;
+int md2_resize_frames(const md2_resize_cfg* cfg,
+                      const unsigned char* src,   /* device: all source images             */
+                      const long long* offsets,   /* HOST [m]: byte offset of image i in src */
+                      const int* src_w, const int* src_h, /* HOST [m]: 1..8192 each        */
+                      const unsigned char* flip,  /* HOST [m] or NULL: mirror after resize */
+                      float* out,                 /* device [m][c][out_h][out_w], 16-B aligned */
+                      unsigned char* out_u8,      /* device, same shape, or NULL; needs quantize */
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,13 @@ struct LidarCfg                                        # md2_lidar_cfg
     vel_depth::Cint
 end
 
+struct ResizeCfg                                       # md2_resize_cfg
+    m::Cint; c::Cint
+    out_h::Cint; out_w::Cint
+    filter::Cint
+    quantize::Cint
+end
+
 struct Jitter                                          # md2_jitter
     brightness::Cfloat; contrast::Cfloat; saturation::Cfloat; hue::Cfloat
     order::NTuple{4, Cuchar}
@@ -803,6 +810,35 @@ function post_process_disparity(disp::ROCArray{Float32}, disp_flipped::ROCArray{
                 (Ptr{Float32}, Ptr{Float32}, Cint, Cint, Cint, Ptr{Float32}, Ptr{Cvoid}),
                 disp, disp_flipped, size(disp, ndims(disp)), size(disp, 2), size(disp, 1), out, stream_ptr()))
     return out
+end
+
+# Frame resize on the device (include/md2.h states every operation of both filters): src holds the
+# decoded images, image i the src_h[i] rows of src_w[i] interleaved c-byte pixels that start at the
+# 0-based byte offsets[i].  Returns the planes (w, h, c, m) as Float32 -- m = 3n frames in order is
+# the batch (w, h, c, 3, n) -- with return_u8 also the N0f8 bytes.  filter = RESIZE_IMRESIZE gives
+# the host loader's bytes, RESIZE_ANTIALIAS the triangle filter widened by the reduction factor.
+# At most RESIZE_MAX_IMAGES images per call.  No host sync.
+const RESIZE_MAX_IMAGES = 64
+const RESIZE_IMRESIZE = 0
+const RESIZE_ANTIALIAS = 1
+function resize_frames(src::ROCVector{UInt8}, offsets::Vector{Int64}, src_w::Vector{Int32}, src_h::Vector{Int32}, h, w;
+                       channels, filter=RESIZE_IMRESIZE, quantize=true, flips=nothing, return_u8=false)
+    m = length(offsets)
+    1 <= m <= RESIZE_MAX_IMAGES || error("1..", RESIZE_MAX_IMAGES, " images per call, got ", m)
+    length(src_w) == m && length(src_h) == m || error("one size per image: ", m)
+    flips === nothing || length(flips) == m || error("one flip per image: ", m)
+    all(offsets .>= 0) && all(offsets .+ Int64.(src_w) .* src_h .* channels .<= length(src)) ||
+        error("every image must lie within src")
+    (!return_u8 || quantize) || error("return_u8 needs quantize")
+    cfg = ResizeCfg(m, channels, h, w, filter, quantize ? 1 : 0)
+    out = ROCArray{Float32}(undef, w, h, channels, m)
+    u8 = return_u8 ? ROCArray{UInt8}(undef, w, h, channels, m) : nothing
+    fl = flips === nothing ? C_NULL : Vector{UInt8}(flips .!= 0)      # ccall keeps its arguments alive
+    check(ccall((:md2_resize_frames, lib), Cint,
+                (Ref{ResizeCfg}, Ptr{UInt8}, Ptr{Clonglong}, Ptr{Cint}, Ptr{Cint}, Ptr{UInt8}, Ptr{Float32}, Ptr{UInt8},
+                 Ptr{Cvoid}),
+                cfg, src, offsets, src_w, src_h, fl, out, u8 === nothing ? C_NULL : u8, stream_ptr()))
+    return return_u8 ? (out, u8) : out
 end
 
 # Colour augmentation (torchvision's ColorJitter; include/md2.h states every operation): x

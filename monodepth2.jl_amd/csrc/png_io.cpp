@@ -340,4 +340,39 @@ int md2_load_kitti_u8(const char* const* paths, int n, int height, int width,
   });
 }
 
+int md2_load_frames_native_u8(const char* const* paths, int n, int c, unsigned char* out, long long slot_bytes,
+                              int* w, int* h, int threads) {
+  MD2_CHECK_ARG(paths && out && w && h && n >= 0 && slot_bytes > 0, "load_frames_native args");
+  MD2_CHECK_ARG(c == 1 || c == 3, "load_frames_native: c must be 1 or 3");
+  return parallel_for(n, threads, [&](int i, std::string& err) {
+    Png p;
+    if (!decode_png(paths[i], p, err)) return false;
+    if (c == 1 ? p.ch != 1 : p.ch < 3) {
+      err = std::string(paths[i]) + ": " + std::to_string(p.ch) + "-channel file where " +
+            (c == 1 ? "8-bit grayscale" : "RGB or RGBA") + " is expected";
+      return false;
+    }
+    const size_t npix = (size_t)p.w * p.h;
+    if ((long long)(npix * c) > slot_bytes) {
+      err = std::string(paths[i]) + ": " + std::to_string(p.w) + "x" + std::to_string(p.h) + "x" +
+            std::to_string(c) + " does not fit a slot of " + std::to_string(slot_bytes) + " bytes";
+      return false;
+    }
+    unsigned char* dst = out + (size_t)i * (size_t)slot_bytes;
+    if (p.ch == c) {
+      std::memcpy(dst, p.px.data(), npix * c);
+    } else {   // RGBA: the first three channels
+      const unsigned char* s = p.px.data();
+      for (size_t k = 0; k < npix; ++k, s += 4, dst += 3) {
+        dst[0] = s[0];
+        dst[1] = s[1];
+        dst[2] = s[2];
+      }
+    }
+    w[i] = p.w;
+    h[i] = p.h;
+    return true;
+  });
+}
+
 }  // extern "C"

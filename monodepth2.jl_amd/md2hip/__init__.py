@@ -19,6 +19,7 @@ from .evaluate import (METRIC_NAMES, chord_to_degrees, depth_errors, evaluate_de
 from .lidar import (kitti_odometry_velo_to_image, kitti_raw_velo_to_image, lidar_depth, load_velodyne,  # noqa: F401
                     post_process_disparity)
 from .color import JITTER_DTYPE, ColorJitter, color_jitter, jitter_params  # noqa: F401
+from .resize import decode_frames, load_frames, resize_frames  # noqa: F401
 
 __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_poses", "lib", "MD2Error",
            "ADAM", "DepthDecoder", "Model", "Pose", "PoseDecoder", "ResidualNetwork", "ResNet",
@@ -33,4 +34,5 @@ __all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_pos
            "JITTER_DTYPE", "ColorJitter", "color_jitter", "jitter_params",
            "eval_pose", "pose_errors", "evaluate_pose", "pose_windows", "chord_to_degrees",
            "load_kitti_poses", "relative_poses",
-           "grad_norm", "decode_guard_state"]
+           "grad_norm", "decode_guard_state",
+           "resize_frames", "load_frames", "decode_frames"]

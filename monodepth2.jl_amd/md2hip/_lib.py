@@ -111,6 +111,16 @@ class GuardState(C.Structure):
                 ("norm", C.c_float), ("coef", C.c_float), ("gscale", C.c_float), ("ok", C.c_int)]
 
 
+RESIZE_MAX_IMAGES = 64   # include/md2.h MD2_RESIZE_MAX_IMAGES
+RESIZE_FILTERS = {"imresize": 0, "antialias": 1}   # MD2_RESIZE_IMRESIZE, MD2_RESIZE_ANTIALIAS
+
+
+class ResizeCfg(C.Structure):
+    """``md2_resize_cfg``."""
+    _fields_ = [("m", C.c_int), ("c", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int), ("filter", C.c_int),
+                ("quantize", C.c_int)]
+
+
 _lib = None
 _load_error = None
 
@@ -234,6 +244,10 @@ _SIGS = {
     "md2_png_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "md2_load_triplets_u8": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, P, P, C.c_int]),
     "md2_load_kitti_u8": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, P, P, C.c_int]),
+    "md2_load_frames_native_u8": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, P, C.c_longlong,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "md2_resize_frames": (C.c_int, [C.POINTER(ResizeCfg), P, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int), P, P, P, P]),
     "md2_smooth_loss_workspace_size": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "md2_smooth_loss_fwd": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P]),
     "md2_smooth_loss_bwd": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, P, P, P]),

@@ -243,16 +243,39 @@ def _parse_calib_P0(line: str) -> np.ndarray:
 
 class KittyDataset(_Dataset):
     """``KittyDataset(image_dir, sequence; target_size=(height, width), augmentations)``
-    (src/kitty.jl:19-44): grayscale ``image_0`` frames, non-overlapping triplets."""
+    (src/kitty.jl:19-44): non-overlapping triplets of one camera's frames.
 
-    def __init__(self, image_dir: str, sequence: str, *, target_size, augmentations=None):
+    ``camera``: ``"image_0"`` / ``"image_1"`` are the grayscale cameras (the reference's), ``"image_2"``
+    / ``"image_3"`` the colour ones (``channels = 3``; they need ``resize="device"``).
+    ``resize="host"`` resizes on the loader's host threads (``md2_load_kitti_u8``, imresize);
+    ``resize="device"`` decodes the frames at their own sizes (``batch_native``) and leaves the resize
+    to ``md2_resize_frames`` on the GPU, which ``DataLoader`` drives; ``filter`` is then
+    ``"imresize"`` (the host path's bytes) or ``"antialias"``."""
+
+    CAMERAS = {"image_0": 1, "image_1": 1, "image_2": 3, "image_3": 3}
+
+    def __init__(self, image_dir: str, sequence: str, *, target_size, augmentations=None,
+                 camera: str = "image_0", resize: str = "host", filter: str = "imresize"):
+        from ._lib import RESIZE_FILTERS
+        if camera not in self.CAMERAS:
+            raise ValueError(f"camera must be one of {sorted(self.CAMERAS)}, got {camera!r}")
+        if resize not in ("host", "device"):
+            raise ValueError(f"resize must be 'host' or 'device', got {resize!r}")
+        if filter not in RESIZE_FILTERS:
+            raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+        if resize == "host" and filter != "imresize":
+            raise ValueError('filter="antialias" needs resize="device": the host path is imresize, without a prefilter')
+        if resize == "host" and self.CAMERAS[camera] != 1:
+            raise ValueError(f'camera="{camera}" is a colour camera: it needs resize="device" '
+                             "(the host path reads 8-bit grayscale)")
         seq_dir = os.path.join(image_dir, "sequences", sequence)
         with open(os.path.join(seq_dir, "calib.txt")) as f:
             K0 = _parse_calib_P0(f.readline())
-        self.frames_dir = os.path.join(seq_dir, "image_0")
+        self.frames_dir = os.path.join(seq_dir, camera)
         files = sorted(os.listdir(self.frames_dir))
         n_frames = len(files)
-        orig = _load_png(os.path.join(self.frames_dir, files[0])).shape[1:]   # (height, width)
+        first = os.path.join(self.frames_dir, files[0])
+        orig = _load_png(first).shape[1:]   # (height, width)
         height, width = target_size
         fx = float(np.mean(np.array(target_size, dtype=np.float64) / np.array(orig))) * K0[0, 0]
         self.K = intrinsics(fx, fx, width // 2, height // 2)
@@ -261,31 +284,67 @@ class KittyDataset(_Dataset):
         self.frame_ids = (1, 2, 3)
         self.total_length = n_frames // len(self.frame_ids)
         self.augmentations = augmentations
-        self.channels = 1
+        self.channels = self.CAMERAS[camera]
         self.u8 = True
+        self.camera, self.resize, self.filter = camera, resize, filter
+        # staging slot of one decoded frame: the first frame's bytes with 4 % headroom (KITTI's
+        # sizes, 1224x370 .. 1242x376, differ by 1.5 %), a multiple of 16
+        need = int(orig[0]) * int(orig[1]) * self.channels
+        self.slot_bytes = (need + need // 25 + 15) // 16 * 16
 
     def __len__(self):
         return self.total_length
 
+    def _paths(self, idx):
+        return [os.path.join(self.frames_dir, "%06d.png" % (i * len(self.frame_ids) + x - 1)).encode()
+                for i in idx for x in self.frame_ids]
+
     def _native_load(self, idx, flips, out, threads):
         from ._lib import check, lib
-        files = [os.path.join(self.frames_dir, "%06d.png" % (i * len(self.frame_ids) + x - 1)).encode()
-                 for i in idx for x in self.frame_ids]
+        if self.resize != "host":
+            raise TypeError('resize="device": the batch comes from batch_native and md2_resize_frames')
+        files = self._paths(idx)
         paths = (C.c_char_p * len(files))(*files)
         w, h = self.resolution
         check(lib().md2_load_kitti_u8(paths, len(idx), h, w, flips.ctypes.data_as(C.c_void_p),
                                       C.c_void_p(_addr(out)), threads), "md2_load_kitti_u8")
 
+    def batch_native(self, idx, seed: int = 0, threads: int = 8, out=None):
+        """Samples ``idx`` decoded at their own sizes (md2_load_frames_native_u8 on ``threads`` host
+        threads), for ``md2hip.resize_frames``: ``(buf, offsets, sizes, flips)`` -- ``buf`` uint8
+        [len(idx) * 3 * slot_bytes] (``out``: a caller buffer, e.g. pinned) holding frame k of the
+        flat list at ``offsets[k] = k * slot_bytes`` as rows of interleaved pixels, ``sizes[k] =
+        (h, w)``, ``flips[k]`` the FlipX coin of its sample."""
+        from ._lib import check, lib
+        if self.resize != "device":
+            raise TypeError('batch_native is the resize="device" route')
+        coins = self._native_flips(idx, seed)
+        if coins is None:
+            raise TypeError('resize="device" supports no augmentation or one FlipX')
+        files = self._paths(idx)
+        n = len(files)
+        if out is None:
+            out = np.empty(n * self.slot_bytes, dtype=np.uint8)
+        w, h = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        check(lib().md2_load_frames_native_u8((C.c_char_p * n)(*files), n, self.channels, C.c_void_p(_addr(out)),
+                                              self.slot_bytes, w.ctypes.data_as(C.POINTER(C.c_int)),
+                                              h.ctypes.data_as(C.POINTER(C.c_int)), threads),
+              "md2_load_frames_native_u8")
+        return (out, np.arange(n, dtype=np.int64) * self.slot_bytes, np.stack([h, w], 1).astype(np.int64),
+                np.repeat(coins, len(self.frame_ids)))
+
     def getobs_u8(self, i: int, seed: int = 0) -> np.ndarray:
         """Sample ``i`` (0-based): frames 3i, 3i+1, 3i+2 (kitty.jl:47-61), each ``imresize``d to
-        the target size and kept N0f8 -> uint8 [3][1][H][W]."""
+        the target size and kept N0f8 -> uint8 [3][C][H][W] (the host restatement; imresize only)."""
         width, height = self.resolution
         sid = i * len(self.frame_ids)
         frames = []
         for x in self.frame_ids:
             img = _load_png_raw(os.path.join(self.frames_dir, "%06d.png" % (sid + x - 1)))
-            if img.dtype != np.uint8 or img.shape[0] != 1:
-                raise TypeError("KITTI image_0 frames are 8-bit grayscale")
+            if img.dtype != np.uint8 or img.shape[0] != self.channels:
+                raise TypeError(f"KITTI {self.camera} frames are 8-bit " + ("grayscale" if self.channels == 1 else "RGB"))
+            if self.filter != "imresize":
+                raise TypeError('filter="antialias" exists on the device only (DataLoader, md2hip.load_frames)')
             frames.append(imresize(img, height, width))
         frames = self._augment(frames, i, seed)
         return np.stack(frames, 0)
@@ -300,9 +359,51 @@ class DChain:
         self.channels = self.datasets[0].channels
         self.resolution = self.datasets[0].resolution
         self.u8 = all(getattr(d, "u8", False) for d in self.datasets)
+        routes = {getattr(d, "resize", "host") for d in self.datasets}
+        if len(routes) > 1:
+            raise ValueError("DChain members mix host and device resize: a batch takes one route -- give every "
+                             'KittyDataset the same resize=, or chain the resize="device" ones on their own')
+        self.resize = routes.pop() if routes else "host"
+        if self.resize == "device":
+            if len({(d.channels, d.filter, tuple(d.resolution)) for d in self.datasets}) > 1:
+                raise ValueError('DChain members with resize="device" must share channels, filter and target size')
+            self.filter = self.datasets[0].filter
 
     def __len__(self):
         return self.bins[-1] if self.bins else 0
+
+    def _groups(self, idx):
+        groups = {}
+        for k, i in enumerate(idx):
+            if not 0 <= i < len(self):
+                raise IndexError(i)
+            bid = next(b for b, edge in enumerate(self.bins) if i < edge)
+            groups.setdefault(bid, []).append((k, i - (self.bins[bid - 1] if bid else 0)))
+        return groups
+
+    @property
+    def slot_bytes(self):
+        return max(d.slot_bytes for d in self.datasets)
+
+    def batch_native(self, idx, seed: int = 0, threads: int = 8, out=None):
+        """Per member dataset one native decode into its own stretch of ``out``; offsets, sizes and
+        flips come back in ``idx`` order (every image carries its own offset)."""
+        n = 3 * len(idx)
+        if out is None:
+            out = np.empty(n * self.slot_bytes, dtype=np.uint8)
+        offsets, sizes = np.zeros(n, dtype=np.int64), np.zeros((n, 2), dtype=np.int64)
+        flips = np.zeros(n, dtype=np.uint8)
+        pos = 0
+        for bid, items in self._groups(idx).items():
+            d = self.datasets[bid]
+            nbytes = 3 * len(items) * d.slot_bytes
+            _, off, sz, fl = d.batch_native([li for _, li in items], seed, threads, out=out[pos:pos + nbytes])
+            for j, (k, _) in enumerate(items):
+                offsets[3 * k:3 * k + 3] = off[3 * j:3 * j + 3] + pos
+                sizes[3 * k:3 * k + 3] = sz[3 * j:3 * j + 3]
+                flips[3 * k:3 * k + 3] = fl[3 * j:3 * j + 3]
+            pos += nbytes
+        return out, offsets, sizes, flips
 
     def getobs(self, i: int, seed: int = 0) -> np.ndarray:
         if not 0 <= i < len(self):
@@ -349,7 +450,11 @@ class DataLoader:
     ``prefetch`` batches in flight, ``workers`` threads in all) into pinned memory.
     ``color_jitter`` (a ``md2hip.ColorJitter``; GPU loaders only): the loader yields ``(x, x_net)``
     instead of x -- x_net is ``color_jitter(x, color_jitter.draw(idx, seed + epoch))``, computed on
-    the side stream right after the batch arrives; x stays the un-augmented batch for the loss."""
+    the side stream right after the batch arrives; x stays the un-augmented batch for the loss.
+    A dataset with ``resize="device"`` (``KittyDataset``; GPU loaders only) is decoded at its frames'
+    own sizes into pinned slots (``batch_native``), copied in one piece and resized on the side stream
+    by ``md2_resize_frames``, FlipX and the N0f8 -> Float32 conversion included; with
+    ``filter="imresize"`` the batch equals the ``resize="host"`` loader's bit for bit."""
 
     def __init__(self, dataset, batch_size: int, *, shuffle: bool = True, seed: int = 0,
                  workers: int = 8, device=None, rank: int = 0, world: int = 1, prefetch: int = 2,
@@ -390,8 +495,11 @@ class DataLoader:
         q: "queue.Queue" = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
 
+        dev_resize = getattr(self.ds, "resize", "host") == "device"
+        if dev_resize and not on_gpu:
+            raise ValueError('resize="device" runs on the GPU: the loader needs a CUDA device')
         use_u8 = on_gpu and self.bytes_h2d and getattr(self.ds, "u8", False)
-        native = self.native and getattr(self.ds, "u8", False) and hasattr(self.ds, "batch_u8")
+        native = dev_resize or (self.native and getattr(self.ds, "u8", False) and hasattr(self.ds, "batch_u8"))
         if use_u8:
             from ._lib import check, lib, ptr
             get = lambda i: self.ds.getobs_u8(i, seed=self.seed + epoch)
@@ -404,6 +512,9 @@ class DataLoader:
 
         def native_batch(idx):
             # the library's PNG decoder on per_call host threads, straight into (pinned) memory
+            if dev_resize:   # frames at their own sizes, one slot each; the GPU resizes
+                buf = torch.empty(len(idx) * 3 * self.ds.slot_bytes, dtype=torch.uint8, pin_memory=True)
+                return self.ds.batch_native(idx, seed=self.seed + epoch, threads=per_call, out=buf)
             buf = torch.empty(shape, dtype=torch.uint8, pin_memory=on_gpu)
             self.ds.batch_u8(idx, seed=self.seed + epoch, threads=per_call, out=buf)
             return buf if use_u8 else torch.from_numpy(_unorm(buf.numpy()))
@@ -434,11 +545,17 @@ class DataLoader:
                                 break
                             host = torch.from_numpy(np.stack(list(pool.map(get, idx)), 0))
                         if on_gpu:
+                            if dev_resize:
+                                host, offsets, sizes, flips = host
                             if not host.is_pinned():
                                 host = host.pin_memory()
                             with torch.cuda.stream(stream):
                                 x = host.to(dev, non_blocking=True)
-                                if use_u8:          # N0f8 bytes -> Float32 on the GPU
+                                if dev_resize:      # one copy, one launch: resize, FlipX and N0f8 -> Float32
+                                    from .resize import resize_frames
+                                    x = resize_frames(x, offsets, sizes, h_, w_, channels=self.ds.channels,
+                                                      filter=self.ds.filter, quantize=True, flips=flips).view(shape)
+                                elif use_u8:        # N0f8 bytes -> Float32 on the GPU
                                     xf = torch.empty(x.shape, dtype=torch.float32, device=dev)
                                     check(lib().md2_unorm8_to_float(ptr(x), ptr(xf), x.numel(),
                                                                     C.c_void_p(stream.cuda_stream)),
