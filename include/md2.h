@@ -240,6 +240,72 @@ int md2_act_backward(const float* out, const float* dout, float* dpre, long long
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The three conv passes with the operand forms the train step feeds them (csrc/conv.h TensorIn /
+ * TensorOut / ConvShape.cin_w / SplitKDefer); md2_conv2d_* above are the case ops == NULL.
+ * Strides count floats; a stride of 0 means contiguous images of the channels that tensor holds.
+ *   input  (fwd, wgrad: x)   channels [0, in_c0) of image b at x + (b % in_bdiv) * in_bs0 +
+ *          (b / in_bdiv) * in_bhi, channels [in_c0, cin) at in1 + b * in_bs1.  in_c0 = 0: cin
+ *          (one tensor); in_bdiv = 0: no frame split.  The two tensors may overlap.
+ *   output (fwd: y, dgrad: dx)   rows [0, out_c0) of image b at y + b * out_bs0, the rest at
+ *          out1 + b * out_bs1; out_c0 = 0: one tensor.  accumulate = 1: out += result.
+ *   wgrad  accumulate = 1: dw += result, db += result.
+ *   cin_w  0 or the input channels of w / dw, [cout][cin_w][kh][kw]: the last cin - cin_w channels
+ *          of x are zero padding (their dx rows come out zero, their filter gradients are not
+ *          produced).  cin_w < cin needs cin % 16 == 0 and cout > 1.
+ * Deferral (fwd, dgrad; defer may be NULL): with defer_reduce = 1 a launch that runs split-K into
+ * a plain output (one tensor, contiguous, no bias / activation / accumulate, stride 1 for dgrad)
+ * skips its reduction: y / dx is NOT written, slab points at [splits][rows][n * pixels] partials
+ * inside the workspace that the caller sums in split order.  splits = 0: declined, the output is
+ * complete.  Forward only: stats != NULL offers [cout][ceil(n*ho*wo / 256)][2] doubles; when the
+ * LDS-halo kernel runs without split-K it writes per 256-pixel tile the fp64 sum and sum of squares
+ * of the fp32 values it stores and sets stats_parts to the tile count (0: not written).
+ * MD2_EINVAL, checked before any HIP call: a null pointer, in_c0 / out_c0 outside their channel
+ * range or below it without a second pointer, a concat split that is not a multiple of 16 on a
+ * cin % 16 == 0 forward, an output stride smaller than its channels, cin_w > cin, cin_w on a
+ * cout = 1 conv or with cin % 16 != 0, stats without defer, db_part without db or with
+ * db_parts < 1, workspace_bytes < md2_conv2d_ex_workspace_size.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct md2_conv_operands {
+  const float* in1;
+  float* out1;
+  long long in_bs0, in_bs1, in_bhi;
+  long long out_bs0, out_bs1;
+  int in_c0, in_bdiv;
+  int out_c0, accumulate;
+  int cin_w;
+} md2_conv_operands;
+
+typedef struct md2_conv_defer {
+  const float* slab; /* out */
+  int defer_reduce;  /* in  */
+  int splits;        /* out */
+  int stats_parts;   /* out */
+} md2_conv_defer;
+
+size_t md2_conv2d_ex_workspace_size(const md2_conv_desc* d, const md2_conv_operands* ops);
+int md2_conv2d_fwd_ex(const md2_conv_desc* d, const md2_conv_operands* ops, const float* x,
+                      const float* w, const float* bias, float* y, double* stats,
+                      md2_conv_defer* defer, void* workspace, size_t workspace_bytes, void* stream);
+int md2_conv2d_dgrad_ex(const md2_conv_desc* d, const md2_conv_operands* ops, const float* dy,
+                        const float* w, float* dx, md2_conv_defer* defer, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* db_part [cout][db_parts]: bias-gradient partials from md2_act_backward_bias (the pass over dy is
+ * then skipped); NULL: summed from dy. */
+int md2_conv2d_wgrad_ex(const md2_conv_desc* d, const md2_conv_operands* ops, const float* x,
+                        const float* dy, float* dw, float* db, const float* db_part, int db_parts,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* md2_act_backward over [n][c][hw] planes (hw % 4 == 0, n*c*hw < 2^31) fused with the per-channel
+ * partial sums of dpre: part [c][md2_act_bias_parts(c, n, hw)].  dpre may alias dout. */
+int md2_act_bias_parts(int c, int n, long long hw);
+int md2_act_backward_bias(const float* out, const float* dout, float* dpre, int n, int c,
+                          long long hw, int act, float* part, void* stream);
+/* Kernel family of the last conv pass launched by the calling thread ("" before the first): px,
+ * px2, px3, px16, halo, halo2d, halo_rfl_dgrad, halo_s2, stem_s2d, head_batched, head_fallback,
+ * whalo, wgrad16, wgrad_px3:<BM>x<BN>c<CW>, wgrad_tile:<BM>x<BN>c<CW>, stem_wgrad_s2d, stem_wgrad.
+ * The string is owned by the library and changes with the next conv call of the thread. */
+const char* md2_conv_last_kernel(void);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling / resampling layers of the networks, [n][c][h][w] planes.
  * MaxPool((3,3), pad=1, stride=2) of the ResNet.jl stem: y [n][c][ho][wo] with
  * ho = (h+1)/2, wo = (w+1)/2, arg = window index kh*3+kw of the first maximum (uint8, kept for

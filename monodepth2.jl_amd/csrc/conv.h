@@ -116,6 +116,14 @@ size_t conv_wgrad_workspace(const ConvShape& s);
 // split products on the bf16 MFMA (issued ceiling 2516 / 6 TFLOP/s fp32-equivalent), 1 = fp32
 // MFMA, 0 = VALU (the Cout = 1 heads)
 int conv_last_arith();
+// kernel family of the last conv kernel launched by this host thread, written at the launch sites
+// (conv_note_kernel): px, px2, px3, px16, halo, halo2d, halo_rfl_dgrad, halo_s2, stem_s2d,
+// head_batched, head_fallback (fwd / dgrad; the stride-2 class launches name their last kernel);
+// whalo, wgrad16, wgrad_px3:<BM>x<BN>c<CW>, wgrad_tile:<BM>x<BN>c<CW> (c0: channel-major columns),
+// stem_wgrad_s2d, stem_wgrad (wgrad).  Reductions, folds and the bias pass do not change it.
+const char* conv_last_kernel();
+// `family`: a string literal; bm > 0 adds the ":<BM>x<BN>c<CW>" tile suffix
+void conv_note_kernel(const char* family, int bm = 0, int bn = 0, int cw = 0);
 int conv_fwd(const ConvShape& s, const TensorIn& x, const float* wpacked, const TensorOut& y,
              ConvWorkspace ws, hipStream_t st, SplitKDefer* defer = nullptr);
 // dX from dY (dY: [N][Cout][Ho][Wo] pre-activation gradient)

@@ -1,5 +1,6 @@
 // Implicit-GEMM conv: weight packing, the planners, selection predicates, workspace sizing,
 // act_backward (the map of the conv files: conv_kernel.h).
+#include <cstdio>
 #include "conv_plan.h"
 #include "conv_lds.h"
 
@@ -210,6 +211,30 @@ int& conv_arith_ref() {
   return v;
 }
 int conv_last_arith() { return conv_arith_ref(); }
+
+// a launch site stores four words; the string is put together when it is asked for
+struct KernelNote {
+  const char* family = "";
+  int bm = 0, bn = 0, cw = 0;
+  char text[48] = "";
+};
+static KernelNote& conv_kernel_note() {
+  static thread_local KernelNote n;
+  return n;
+}
+void conv_note_kernel(const char* family, int bm, int bn, int cw) {
+  KernelNote& n = conv_kernel_note();
+  n.family = family;
+  n.bm = bm;
+  n.bn = bn;
+  n.cw = cw;
+}
+const char* conv_last_kernel() {
+  KernelNote& n = conv_kernel_note();
+  if (n.bm == 0) return n.family;
+  snprintf(n.text, sizeof n.text, "%s:%dx%dc%d", n.family, n.bm, n.bn, n.cw);
+  return n.text;
+}
 
 int conv_pack_batch(const PackJob* dev_jobs, int njobs, long total_blocks, hipStream_t st) {
   if (njobs == 0) return MD2_OK;

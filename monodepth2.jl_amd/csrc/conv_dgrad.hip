@@ -124,7 +124,11 @@ int conv_dgrad(const ConvShape& s, const float* dy, const float* wpacked_d, cons
     j.dy = dy;
     j.dx = dx.p0;
     j.dxbs = dx.bs0;
-    if (s.reflect && !dx.accumulate && !heads_job_unfit(j)) return heads_bwd(&j, 1, nullptr, 0, st);
+    if (s.reflect && !dx.accumulate && !heads_job_unfit(j)) {
+      conv_note_kernel("head_batched");
+      return heads_bwd(&j, 1, nullptr, 0, st);
+    }
+    conv_note_kernel("head_fallback");
     return head_dgrad(j, s.reflect, dx.accumulate, st);
   }
   ConvArgs a{};
@@ -212,6 +216,7 @@ int conv_dgrad(const ConvShape& s, const float* dy, const float* wpacked_d, cons
       ak.slab = (float*)ws.ptr;
     }
     conv_arith_ref() = 6;
+    conv_note_kernel("halo_s2");
     MD2_TRY(halo_s2_launch(ak, h2.items, h2.splits, st));
     if (h2.splits > 1) {
       ConvArgs ar = a;

@@ -25,7 +25,11 @@ int conv_fwd(const ConvShape& s, const TensorIn& x, const float* wpacked, const 
     j.bias = y.bias;
     j.y = y.p0;
     j.ybs = y.bs0;
-    if (s.reflect && !y.accumulate && !heads_job_unfit(j)) return heads_fwd(&j, 1, y.act, st);
+    if (s.reflect && !y.accumulate && !heads_job_unfit(j)) {
+      conv_note_kernel("head_batched");
+      return heads_fwd(&j, 1, y.act, st);
+    }
+    conv_note_kernel("head_fallback");
     return head_fwd(j, s.reflect, y.act, y.accumulate, st);
   }
   ConvArgs a{};
@@ -53,6 +57,7 @@ int conv_fwd(const ConvShape& s, const TensorIn& x, const float* wpacked, const 
   }
   if (stem_s2d_applies(s, x, y)) {   // (statistics: the separate pass)
     conv_arith_ref() = 6;
+    conv_note_kernel("stem_s2d");
     return stem_s2d_launch(s, a, st);
   }
   const bool bk32 = conv_tap_major(s, 0) && s.Cin % 32 == 0 && (x.c0 >= s.Cin || x.c0 % 32 == 0);

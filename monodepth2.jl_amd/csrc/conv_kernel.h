@@ -4,6 +4,7 @@
 // workspace sizing, act_backward).  conv_px_launch.h: the fwd / dgrad kernels (conv_px*.inc) and
 // launchers of conv_fwd.hip and conv_dgrad.hip.  conv_wgrad.hip: conv_wgrad_kernels.inc,
 // conv_wpx3.inc, launchers, conv_wgrad.  conv_halo.hip / conv_stem.hip: conv_halo.inc / conv_stem.inc.
+// conv_api.hip: the C entry points that carry the executor's operand forms (md2_conv2d_*_ex; no kernels).
 //
 // All three passes are one GEMM shape  C[M][N] = sum_k A[k][m] * B[k][n]  computed with the
 // exact-fp32 MFMA v_mfma_f32_32x32x2_f32 (64 lanes: A[i=l&31][k=l>>5], B[k=l>>5][j=l&31]; C/D:

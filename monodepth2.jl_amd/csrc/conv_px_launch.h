@@ -92,6 +92,7 @@ int launch_px_tile(const ConvShape& s, const ConvArgs& a, bool tap, int bk, dim3
     if constexpr (BM >= 32 && BN % 64 == 0 && WM * WN == 4) {                                    \
       if (v3) {                                                                                  \
         conv_arith_ref() = 6;                                                                    \
+        conv_note_kernel("px3");                                                                 \
         if (px3_terms() == 6)                                                                    \
           hipLaunchKernelGGL((conv_px3_kernel<MODE, BM, BN, WM, WN, KS, KS, SS, RR, 16, 6>), grid, \
                              dim3(256), 0, st, a);                                               \
@@ -105,6 +106,7 @@ int launch_px_tile(const ConvShape& s, const ConvArgs& a, bool tap, int bk, dim3
     if constexpr (BM >= 64 && BN % 64 == 0) {                                                    \
       if (v2) {                                                                                  \
         conv_arith_ref() = 1;                                                                    \
+        conv_note_kernel("px2");                                                                 \
         if (bk == 32)                                                                            \
           hipLaunchKernelGGL((conv_px2_kernel<MODE, BM, BN, WM, WN, KS, KS, SS, RR, 32>), grid,  \
                              dim3(256), 0, st, a);                                               \
@@ -120,6 +122,7 @@ int launch_px_tile(const ConvShape& s, const ConvArgs& a, bool tap, int bk, dim3
       return MD2_EINVAL;                                                                         \
     }                                                                                            \
     conv_arith_ref() = 1;                                                                        \
+    conv_note_kernel("px");                                                                      \
     if (tap && bk == 32)                                                                         \
       hipLaunchKernelGGL((conv_px_kernel<MODE, 1, BM, BN, 32, WM, WN, KS, KS, SS, RR>), grid,    \
                          dim3(256), 0, st, a);                                                   \
@@ -144,6 +147,7 @@ template <int MODE>
 int launch_px16(const ConvShape& s, ConvArgs& a, hipStream_t st) {
   a.slab = nullptr;
   conv_arith_ref() = 1;
+  conv_note_kernel("px16");
   a.g.kper = (int)round_up(a.g.K, 16);
   static const int bn = tuning_knob("MD2_PX16_BN", 128);   // 128 measured faster on every decoder shape
   const bool big = bn == 256;
@@ -205,6 +209,7 @@ int launch_px(const ConvShape& s, ConvArgs& a, const Plan& p_in, ConvWorkspace w
                       !oo.accumulate && oo.c0 >= a.g.M && oo.bs0 == (long)a.g.M * a.fd_pix.d;
     a.bn_part = bnst ? stats : nullptr;
     conv_arith_ref() = 6;
+    conv_note_kernel(MODE == 1 && a.hx_ext ? "halo_rfl_dgrad" : hp.d2 ? "halo2d" : "halo");
     rc = hp.d2 ? halo2d_launch(MODE, a, hp.mw, hp.splits, s.reflect, st)
                : halo_launch(MODE, a, hp.items, hp.splits, s.reflect, st);
     a.bn_part = nullptr;

@@ -49,14 +49,17 @@ void launch_w_cw(const ConvArgs& a, dim3 grid, hipStream_t st) {
   if constexpr (CW <= BN && CW % 32 == 0 && BM % 32 == 0 && BN % 32 == 0) {
     if (wgrad_px3_on() && a.HoWo % 2 == 0) {
       conv_arith_ref() = 6;
+      conv_note_kernel("wgrad_px3", BM, BN, CW);
       launch_wpx3<BM, BN, WM, WN, KS, SS, RR, CW, 2>(a, grid, st);
       return;
     }
   }
   conv_arith_ref() = 1;
-  if constexpr (CW <= BN)
+  if constexpr (CW <= BN) {
+    conv_note_kernel("wgrad_tile", BM, BN, CW);
     hipLaunchKernelGGL((conv_wgrad_tap_kernel<BM, BN, 32, WM, WN, KS, KS, SS, RR, CW>), grid,
                        dim3(256), 0, st, a);
+  }
 }
 
 template <int BM, int BN, int WM, int WN, int KS, int SS, int RR>
@@ -64,6 +67,7 @@ int launch_w(int cw, const ConvArgs& a, dim3 grid, hipStream_t st) {
   switch (cw) {
     case 0:
       conv_arith_ref() = 1;
+      conv_note_kernel("wgrad_tile", BM, BN, 0);
       hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, 32, WM, WN, KS, KS, SS, RR>), grid, dim3(256), 0,
                          st, a);
       break;
@@ -90,7 +94,11 @@ int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw
     j.dy = dy;
     j.dw = dw;
     j.db = db;
-    if (s.reflect && !accumulate && !heads_job_unfit(j)) return heads_bwd(&j, 1, ws.ptr, ws.bytes, st);
+    if (s.reflect && !accumulate && !heads_job_unfit(j)) {
+      conv_note_kernel("head_batched");
+      return heads_bwd(&j, 1, ws.ptr, ws.bytes, st);
+    }
+    conv_note_kernel("head_fallback");
     return head_wgrad(j, s.reflect, accumulate, ws.ptr, ws.bytes, st);
   }
   const WPlan p = plan_wgrad(s, x.c0);
@@ -136,15 +144,18 @@ int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw
     a.hx_nchunk = hx.nchunk;
     a.hx_cper = hx.cper;
     conv_arith_ref() = 6;
+    conv_note_kernel("whalo");
     rc = whalo_launch(a, hx.items, cdiv(hx.r * s.W, 16), hx.splits, st);
     if (rc) return rc;
   }
   if (stem2) {
     conv_arith_ref() = 6;
+    conv_note_kernel("stem_wgrad_s2d");
     rc = stem_wgrad_s2d_launch(s, a, st);
   }
   if (rc == MD2_ENOTSUP && p.tile == WSTEM) {
     conv_arith_ref() = 1;
+    conv_note_kernel("stem_wgrad");
     const dim3 gs((unsigned)p.splits);
     switch (s.Cin) {
       case 1: hipLaunchKernelGGL(conv_wgrad_stem_kernel<1>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
@@ -156,6 +167,7 @@ int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw
   }
   if (rc == MD2_ENOTSUP && p.tile == W16x144) {
     conv_arith_ref() = 1;
+    conv_note_kernel("wgrad16");
     grid.y = 1;
     if (p.BM == 64) {
       if (s.reflect)

@@ -46,6 +46,20 @@ class ConvDesc(C.Structure):
                                        "reflect", "act")]
 
 
+class ConvOperands(C.Structure):
+    """``md2_conv_operands``."""
+    _fields_ = [("in1", C.c_void_p), ("out1", C.c_void_p),
+                ("in_bs0", C.c_longlong), ("in_bs1", C.c_longlong), ("in_bhi", C.c_longlong),
+                ("out_bs0", C.c_longlong), ("out_bs1", C.c_longlong),
+                ("in_c0", C.c_int), ("in_bdiv", C.c_int), ("out_c0", C.c_int), ("accumulate", C.c_int),
+                ("cin_w", C.c_int)]
+
+
+class ConvDefer(C.Structure):
+    """``md2_conv_defer``."""
+    _fields_ = [("slab", C.c_void_p), ("defer_reduce", C.c_int), ("splits", C.c_int), ("stats_parts", C.c_int)]
+
+
 class ModelCfg(C.Structure):
     """``md2_model_cfg``."""
     _fields_ = [
@@ -160,6 +174,16 @@ _SIGS = {
     "md2_conv2d_dgrad": (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P]),
     "md2_conv2d_wgrad": (C.c_int, [C.POINTER(ConvDesc), P, P, P, P, P, P]),
     "md2_act_backward": (C.c_int, [P, P, P, C.c_longlong, C.c_int, P]),
+    "md2_conv2d_ex_workspace_size": (C.c_size_t, [C.POINTER(ConvDesc), C.POINTER(ConvOperands)]),
+    "md2_conv2d_fwd_ex": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvOperands), P, P, P, P, P,
+                                     C.POINTER(ConvDefer), P, C.c_size_t, P]),
+    "md2_conv2d_dgrad_ex": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvOperands), P, P, P, C.POINTER(ConvDefer), P,
+                                       C.c_size_t, P]),
+    "md2_conv2d_wgrad_ex": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvOperands), P, P, P, P, P, C.c_int, P,
+                                       C.c_size_t, P]),
+    "md2_act_bias_parts": (C.c_int, [C.c_int, C.c_int, C.c_longlong]),
+    "md2_act_backward_bias": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_longlong, C.c_int, P, P]),
+    "md2_conv_last_kernel": (C.c_char_p, []),
     "md2_adam": (C.c_int, [P, P, P, P, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float,
                             C.c_int, C.c_float, P]),
     "md2_maxpool3s2_fwd": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P]),

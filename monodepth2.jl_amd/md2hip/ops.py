@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _lib
-from ._lib import ConvDesc, check, lib, ptr, stream_of
+from ._lib import ConvDesc, ConvOperands, check, lib, ptr, stream_of
 
 ACT = {None: 0, "identity": 0, "relu": 1, "elu": 2, "sigmoid": 3}
 
@@ -62,6 +62,98 @@ def conv2d_wgrad(x, dy, w_shape, stride=1, pad=0, reflect=False, bias=True):
     check(lib().md2_conv2d_wgrad(C.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(db), ptr(_ws(d, x.device)),
                                  stream_of(x.device)), "md2_conv2d_wgrad")
     return dw, db
+
+
+def conv_operands(in1=None, in_c0=0, in_bs0=0, in_bs1=0, in_bdiv=0, in_bhi=0, out1=None, out_c0=0,
+                  out_bs0=0, out_bs1=0, accumulate=False, cin_w=0) -> ConvOperands:
+    """``md2_conv_operands``: the operand forms of the train step (include/md2.h).  ``in1`` /
+    ``out1`` are tensors (or views) whose first element is the second base pointer; strides count
+    floats, 0 = contiguous."""
+    o = ConvOperands()
+    o.in1 = None if in1 is None else in1.data_ptr()
+    o.out1 = None if out1 is None else out1.data_ptr()
+    o.in_bs0, o.in_bs1, o.in_bhi, o.out_bs0, o.out_bs1 = in_bs0, in_bs1, in_bhi, out_bs0, out_bs1
+    o.in_c0, o.in_bdiv, o.out_c0, o.accumulate, o.cin_w = in_c0, in_bdiv, out_c0, int(accumulate), cin_w
+    o._keep = (in1, out1)
+    return o
+
+
+def conv_last_kernel() -> str:
+    """Kernel family of the calling thread's last conv launch (``md2_conv_last_kernel``)."""
+    return lib().md2_conv_last_kernel().decode()
+
+
+def conv2d_ex_workspace(d, o, dev):
+    import torch
+    nbytes = lib().md2_conv2d_ex_workspace_size(C.byref(d), C.byref(o) if o is not None else None)
+    if nbytes == 0:
+        raise ValueError("md2_conv2d_ex_workspace_size: invalid conv description")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+
+
+def _ex_result(defer, ws, rows, cols):
+    info = {"kernel": conv_last_kernel(), "splits": 0, "slab": None, "stats_parts": 0}
+    if defer is not None:
+        info["splits"], info["stats_parts"] = defer.splits, defer.stats_parts
+        if defer.splits > 0:
+            off = (defer.slab - ws.data_ptr()) // 4
+            info["slab"] = ws[off:off + defer.splits * rows * cols].view(defer.splits, rows, cols)
+    return info
+
+
+def conv2d_fwd_ex(d, o, x, weight, bias, y, defer=False, stats=None, ws=None):
+    """``md2_conv2d_fwd_ex`` on caller-owned buffers: ``x`` / ``y`` (tensors or views) give the
+    first base pointers, ``o`` (:func:`conv_operands`) the rest.  ``defer``: ask for the split-K
+    deferral; ``stats``: a float64 tensor [cout, ceil(n*ho*wo/256), 2] offered to the epilogue.
+    Returns {kernel, splits, slab ([splits, cout, n*ho*wo] view of the workspace, or None),
+    stats_parts}; keep the result alive while ``slab`` is read."""
+    ws = conv2d_ex_workspace(d, o, x.device) if ws is None else ws
+    df = None
+    if defer or stats is not None:
+        df = _lib.ConvDefer()
+        df.defer_reduce = int(bool(defer))
+    ho, wo = out_hw(d.h, d.w, d.kh, d.stride, d.pad)
+    check(lib().md2_conv2d_fwd_ex(C.byref(d), C.byref(o) if o is not None else None, ptr(x), ptr(weight),
+                                  ptr(bias), ptr(y), ptr(stats), C.byref(df) if df is not None else None,
+                                  ptr(ws), ws.numel() * 4, stream_of(x.device)), "md2_conv2d_fwd_ex")
+    return _ex_result(df, ws, d.cout, d.n * ho * wo)
+
+
+def conv2d_dgrad_ex(d, o, dy, weight, dx, defer=False, ws=None):
+    """``md2_conv2d_dgrad_ex``: dx (split / strided / accumulated as ``o`` says) from dy."""
+    ws = conv2d_ex_workspace(d, o, dy.device) if ws is None else ws
+    df = None
+    if defer:
+        df = _lib.ConvDefer()
+        df.defer_reduce = 1
+    check(lib().md2_conv2d_dgrad_ex(C.byref(d), C.byref(o) if o is not None else None, ptr(dy), ptr(weight),
+                                    ptr(dx), C.byref(df) if df is not None else None, ptr(ws), ws.numel() * 4,
+                                    stream_of(dy.device)), "md2_conv2d_dgrad_ex")
+    return _ex_result(df, ws, d.cin, d.n * d.h * d.w)
+
+
+def conv2d_wgrad_ex(d, o, x, dy, dw, db=None, db_part=None, ws=None):
+    """``md2_conv2d_wgrad_ex``: dw [cout, cin_w or cin, k, k] and db (stored, or accumulated with
+    ``o.accumulate``); ``db_part`` [cout, parts] from :func:`act_backward_bias`."""
+    ws = conv2d_ex_workspace(d, o, x.device) if ws is None else ws
+    check(lib().md2_conv2d_wgrad_ex(C.byref(d), C.byref(o) if o is not None else None, ptr(x), ptr(dy), ptr(dw),
+                                    ptr(db), ptr(db_part), 0 if db_part is None else db_part.shape[1], ptr(ws),
+                                    ws.numel() * 4, stream_of(x.device)), "md2_conv2d_wgrad_ex")
+    return _ex_result(None, ws, 0, 0)
+
+
+def act_backward_bias(out, dout, act):
+    """:func:`act_backward` over [n, c, h, w] fused with the per-channel partial sums of dpre:
+    returns (dpre, part [c, parts])."""
+    import torch
+    n, c = out.shape[0], out.shape[1]
+    hw = out[0, 0].numel()
+    parts = lib().md2_act_bias_parts(c, n, hw)
+    dpre = torch.empty_like(dout)
+    part = torch.empty(c, max(parts, 1), dtype=torch.float32, device=out.device)
+    check(lib().md2_act_backward_bias(ptr(out), ptr(dout), ptr(dpre), n, c, hw, ACT[act], ptr(part),
+                                      stream_of(out.device)), "md2_act_backward_bias")
+    return dpre, part
 
 
 def act_backward(out, dout, act):
