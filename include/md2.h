@@ -998,6 +998,85 @@ int md2_resize_frames(const md2_resize_cfg* cfg,
                       unsigned char* out_u8,      /* device, same shape, or NULL; needs quantize */
                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Loss tail over S = 1..MD2_MAX_SOURCES sources, each LEARNED or FIXED -- Monodepth2's stereo
+ * supervision ("MS": both temporal sources and the other camera of the rig; "S": that camera
+ * alone).  Additive: MD2_ABI_VERSION is unchanged, and md2_loss_fwd_bwd keeps its code path.
+ *
+ * A LEARNED source (pose_block >= 0) is warped by composeT(so3_exp_map(rvec), tvec, invert) of
+ * row pose[pose_block * n + i] and its pose receives a gradient.  A FIXED source (pose_block == -1)
+ * is warped by the caller's transform Rt[i] = (R row-major (9), t (3)) -- for a rectified stereo
+ * rig R = I and t = (+-baseline, 0, 0) -- which is data: it is read, never differentiated.
+ * The pose blocks of the learned sources must be 0..L-1, each once (L = number of learned
+ * sources); pose and out->d_pose are [L * n][6], and with L = 0 both may be NULL (d_pose is not
+ * written).
+ * Each source is its own tensor: sample i's [c][h][w] frame is at frames + i * sample_stride
+ * (floats), so a source may be a frame inside x[n][3][c][h][w] (frames = x + f * c*h*w,
+ * sample_stride = 3*c*h*w) or a separate [n][c][h][w] tensor (sample_stride = c*h*w).  Likewise
+ * `target` with target_sample_stride.  cfg->target, src0, src1, invert_mask and x_*_stride are
+ * not read; everything else in cfg means what it means to md2_loss_fwd_bwd.
+ *
+ * Per pixel and scale: photometric_loss of every source warped through the scale's depth, then the
+ * FIRST argmin over the sources in the order given (strict <: a tie goes to the earlier source),
+ * then the automask, which wins ties (lmin < automask keeps the source).  Only the selected
+ * source's adjoint is formed.  Sums over sources (d depth) run in ascending source order.
+ * Outputs as md2_loss_out states, with: vis_sel 0..S-1 or -1; vis_warped [S][n][c][h][w];
+ * vis_cell [nscales][S][n][h][w]; d_pose [L*n][6].
+ * With two learned sources that point at frames src0 / src1 of x, every output equals
+ * md2_loss_fwd_bwd's bit for bit (the per-source arithmetic is the same, operation for operation).
+ *
+ * md2_automasking_loss_sources: out [n][h][w] = min over the S raw sources of
+ * photometric_loss(source, target), first source on ties; with two sources the bits of
+ * md2_automasking_loss.  Only frames and sample_stride of each source are read.
+ *
+ * MD2_EINVAL (checked before any HIP call): a null cfg, sources, target, disp, out, out->loss or
+ * workspace; nsrc outside 1..MD2_MAX_SOURCES; a source without frames; a learned source with a
+ * null pose; a fixed source with a null Rt; pose blocks that are not 0..L-1 each once; c not 1
+ * or 3; bad dims.  md2_loss_sources_workspace_size returns 0 for a null cfg or a bad nsrc.
+ * ---------------------------------------------------------------------------------------- */
+#define MD2_MAX_SOURCES 3
+typedef struct md2_loss_source {
+  const float* frames;        /* device; sample i's frame at frames + i*sample_stride, [c][h][w] */
+  long long sample_stride;    /* floats                                                          */
+  int pose_block;             /* >= 0: learned, rows pose[pose_block*n + i]; -1: fixed          */
+  int invert;                 /* learned only: composeT's inverse_transform                      */
+  const float* Rt;            /* fixed only: device [n][12], R row-major then t                  */
+} md2_loss_source;
+size_t md2_loss_sources_workspace_size(const md2_loss_cfg* cfg, int nsrc);
+int md2_loss_fwd_bwd_sources(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
+                             const float* target, long long target_sample_stride,
+                             const float* const* disp, const float* pose, const float* automask,
+                             float dloss, const md2_loss_out* out, void* workspace, void* stream);
+int md2_automasking_loss_sources(int nsrc, const md2_loss_source* sources, const float* target,
+                                 long long target_sample_stride, int n, int c, int h, int w,
+                                 float* out, void* stream);
+
+/* The training entry points with a stereo source, modelled on the _aug pair (x_net as there; NULL or
+ * x: the networks read x).  x_stereo [batch][c][h][w] is the other camera's frame at the target's
+ * time and stereo_Rt [batch][12] its fixed transform (R row-major, t).  The networks never see
+ * x_stereo: only the loss tail and the automask read it.
+ *   temporal = 1 ("MS"): the sources of the loss are cfg.src0, cfg.src1 (learned, as in the plain
+ *     call) and the stereo frame (fixed), in that order -- Monodepth2's [0, -1, 1, "s"].
+ *   temporal = 0 ("S"): the only source is the stereo frame.  The pose network still runs and
+ *     receives a zero d_pose, so its gradient is exactly zero; backward segments, data-parallel
+ *     buckets and the captured graph keep their shape.
+ * auto_loss == NULL with cfg.automasking: the library takes the automask over the same sources the
+ * loss uses (md2_automasking_loss_sources).  The result equals, bit for bit, md2_model_forward(x_net)
+ * followed by md2_loss_fwd_bwd_sources on those sources (sigmoid_grad = 0) and
+ * md2_model_backward_from.  The graph variant copies x_stereo and stereo_Rt into executor-owned
+ * buffers on each call and re-captures when the presence of the stereo source or `temporal`
+ * changes; the gradient guard needs nothing new.  The sources workspace is allocated at the first
+ * stereo call.  MD2_EINVAL: a null x_stereo or stereo_Rt, temporal not 0 or 1.  MPI mode
+ * (embedding_levels > 0): MD2_ENOTSUP.  Test mode: MD2_ESTATE.  md2_model_train_step_dp has no
+ * stereo form. */
+int md2_model_forward_loss_stereo(md2_model* m, const float* x, const float* x_net, const float* x_stereo,
+                                  const float* stereo_Rt, int temporal, const float* auto_loss,
+                                  float* loss, float* terms, void* stream);
+int md2_model_train_step_graph_stereo(md2_model* m, const float* x, const float* x_net,
+                                      const float* x_stereo, const float* stereo_Rt, int temporal,
+                                      const float* auto_loss, float* adam_m, float* adam_v, float lr,
+                                      int step, float* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,13 @@ struct LossOut                                         # md2_loss_out
     vis_cell::Ptr{Int32}                               # parity diagnostics (not used here)
 end
 
+const MAX_SOURCES = 3                                  # include/md2.h MD2_MAX_SOURCES
+struct LossSource                                      # md2_loss_source
+    frames::Ptr{Float32}; sample_stride::Clonglong
+    pose_block::Cint; invert::Cint
+    Rt::Ptr{Float32}
+end
+
 struct WarpCfg                                         # md2_warp_cfg
     n::Cint; c::Cint; width::Cint; height::Cint; dw::Cint; dh::Cint
     K::NTuple{9,Cfloat}; invK::NTuple{9,Cfloat}
@@ -329,6 +336,26 @@ function train_loss(m::HIPModel, x::ROCArray{Float32,5}, auto_loss, cache, param
     _train_loss(m, m.θ, x, auto_loss, do_visualization, x_net)     # m.θ read in traced code: accum_param
 end
 
+"""
+    train_loss_stereo(m, x, x_stereo, stereo_Rt, auto_loss, cache, params; temporal=true, x_net=nothing)
+
+`train_loss` with stereo supervision (md2_model_forward_loss_stereo): `x_stereo` (W,H,C,n) is the
+other camera's frame at the target's time, `stereo_Rt` (12,n) its fixed transform
+(`stereo_transforms`).  `temporal = true` is "MS", the loss over both temporal sources and the stereo
+frame; `temporal = false` is "S", the stereo frame alone (the pose network's gradient is zero).
+Returns `(loss, nothing, nothing, nothing)`; differentiable like `train_loss` (same rrule).
+"""
+function train_loss_stereo(m::HIPModel, x::ROCArray{Float32,5}, x_stereo::ROCArray{Float32,4},
+                           stereo_Rt::ROCArray{Float32,2}, auto_loss, cache, params; temporal::Bool=true,
+                           x_net=nothing)
+    check_config(m, cache, params)
+    x_net === nothing || size(x_net) == size(x) || error("x_net must have x's size")
+    W, H, C, _, n = size(x)
+    size(x_stereo) == (W, H, C, n) || error("x_stereo must be (W,H,C,n) = ", (W, H, C, n))
+    size(stereo_Rt) == (12, n) || error("stereo_Rt must be (12,n) = ", (12, n))
+    _train_loss(m, m.θ, x, auto_loss, false, x_net, (x = x_stereo, Rt = stereo_Rt, temporal = temporal))
+end
+
 # The executor's kernels, buffers and loss-tail weights are built for ONE (Params, TrainCache)
 # (md2_model_cfg).  The reference reads them per call (src/training.jl:40-67), so a caller passing
 # a different cache / params must get an error, not the build-time config's loss.
@@ -351,11 +378,17 @@ function check_config(m::HIPModel, cache, params)
 end
 
 function _train_loss(m::HIPModel, θ::ROCVector{Float32}, x::ROCArray{Float32,5}, auto_loss,
-                     do_visualization::Bool, x_net=nothing)
+                     do_visualization::Bool, x_net=nothing, stereo=nothing)
     θ === m.θ || error("train_loss: θ must be the model's own parameter vector")
     m.packed || repack!(m)               # θ may have been updated in place since the last step
     loss = ROCVector{Float32}(undef, 1)
-    if x_net === nothing
+    if stereo !== nothing                # MS (temporal) or S: the loss and the automask read stereo.x
+        check(ccall((:md2_model_forward_loss_stereo, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float32},
+                     Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                    m.handle, x, ptr(x_net), stereo.x, stereo.Rt, stereo.temporal ? 1 : 0, ptr(auto_loss), loss,
+                    C_NULL, stream_ptr()))
+    elseif x_net === nothing
         check(ccall((:md2_model_forward_loss, lib), Cint,
                     (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
                     m.handle, x, ptr(auto_loss), loss, C_NULL, stream_ptr()))
@@ -406,8 +439,8 @@ end
 # expected to update θ next, so the packed weights are marked stale (re-packed by the next
 # train_loss, or already by the library's own update!).
 function ChainRulesCore.rrule(::typeof(_train_loss), m::HIPModel, θ::ROCVector{Float32}, x, auto_loss,
-                              do_visualization::Bool, x_net=nothing)
-    y = _train_loss(m, θ, x, auto_loss, do_visualization, x_net)
+                              do_visualization::Bool, x_net=nothing, stereo=nothing)
+    y = _train_loss(m, θ, x, auto_loss, do_visualization, x_net, stereo)
     function train_loss_pullback(Δ)
         Δl = unthunk(Δ[1])
         Δl = Δl isa AbstractZero ? 0f0 : Float32(Δl)
@@ -415,7 +448,7 @@ function ChainRulesCore.rrule(::typeof(_train_loss), m::HIPModel, θ::ROCVector{
                     m.handle, Δl, stream_ptr()))
         gradient!(m)
         m.packed = false
-        return (NoTangent(), NoTangent(), copy(m.∇θ), NoTangent(), NoTangent(), NoTangent(), NoTangent())
+        return (NoTangent(), NoTangent(), copy(m.∇θ), NoTangent(), NoTangent(), NoTangent(), NoTangent(), NoTangent())
     end
     return y, train_loss_pullback
 end
@@ -752,6 +785,80 @@ function static_scores(x::ROCArray{Float32,5}; target_id=2, source_ids=(1, 3))
     return Array(scores)
 end
 
+# Stereo supervision (include/md2.h, "Loss tail over S sources"): the loss tail over the two temporal
+# sources of x (learned poses) and a stereo frame with a fixed transform ("MS", temporal = true), or
+# over the stereo frame alone ("S").  x (W,H,C,3,n); x_stereo (W,H,C,n); stereo_Rt (12,n) from
+# stereo_transforms; disps as the model emits them; pose (6,2n) (not read in S mode).
+# Returns (loss, d_disp, d_pose) on the device, d_pose (6,2n) or nothing in S mode.  Data-only
+# arguments; the caller chains d_disp / d_pose into the model's pullback.
+"""
+    stereo_transforms(sides, flips; baseline = 0.1f0)
+
+(12, n) Float32: R = I (row-major) and t = (side_sign * flip_sign * baseline, 0, 0) per sample;
+side_sign is -1 for a left-camera target (`:l`) and +1 for a right one, flip_sign -1 for a mirrored
+sample -- Monodepth2's `stereo_T[0, 3] = side_sign * baseline_sign * 0.1`.  0.1 against KITTI's
+0.54 m baseline is the `scale = 5.4` of `depth_errors(...; median_scaling=false)`.
+"""
+function stereo_transforms(sides, flips; baseline = 0.1f0)
+    length(sides) == length(flips) || error("sides and flips differ in length")
+    Rt = zeros(Float32, 12, length(sides))
+    for (i, (s, f)) in enumerate(zip(sides, flips))
+        s in (:l, :r) || error("side must be :l or :r")
+        Rt[1, i] = Rt[5, i] = Rt[9, i] = 1f0
+        Rt[10, i] = (s == :l ? -1f0 : 1f0) * (f ? -1f0 : 1f0) * Float32(baseline)
+    end
+    return Rt
+end
+
+function stereo_sources(x::ROCArray{Float32,5}, x_stereo::ROCArray{Float32,4}, stereo_Rt::ROCArray{Float32,2},
+                        target_id, source_ids, temporal::Bool)
+    W, H, C, L, n = size(x)
+    size(x_stereo) == (W, H, C, n) || error("x_stereo must be (W,H,C,n) = ", (W, H, C, n))
+    size(stereo_Rt) == (12, n) || error("stereo_Rt must be (12,n) = ", (12, n))
+    fs = W * H * C
+    src = LossSource[]
+    if temporal
+        length(source_ids) == 2 || error("two temporal sources")
+        for (k, sid) in enumerate(source_ids)
+            push!(src, LossSource(pointer(x) + 4 * (sid - 1) * fs, L * fs, k - 1, sid < target_id ? 1 : 0, C_NULL))
+        end
+    end
+    push!(src, LossSource(pointer(x_stereo), fs, -1, 0, pointer(stereo_Rt)))
+    return src
+end
+
+function automasking_loss_sources(x::ROCArray{Float32,5}, x_stereo::ROCArray{Float32,4}; target_id=2,
+                                  source_ids=(1, 3), temporal::Bool=true)
+    W, H, C, L, n = size(x); fs = W * H * C
+    src = stereo_sources(x, x_stereo, ROCArray(zeros(Float32, 12, n)), target_id, source_ids, temporal)
+    out = ROCArray{Float32}(undef, W, H, 1, n)
+    check(ccall((:md2_automasking_loss_sources, lib), Cint,
+                (Cint, Ptr{LossSource}, Ptr{Float32}, Clonglong, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{Cvoid}),
+                length(src), src, pointer(x) + 4 * (target_id - 1) * fs, L * fs, n, C, H, W, out, stream_ptr()))
+    return out
+end
+
+function loss_tail_sources(cfg::LossCfg, disps, pose, x::ROCArray{Float32,5}, x_stereo::ROCArray{Float32,4},
+                           stereo_Rt::ROCArray{Float32,2}, auto_loss; target_id=2, source_ids=(1, 3),
+                           temporal::Bool=true, dloss=1f0)
+    W, H, C, L, n = size(x); fs = W * H * C
+    src = stereo_sources(x, x_stereo, stereo_Rt, target_id, source_ids, temporal)
+    nsrc = length(src)
+    loss = ROCVector{Float32}(undef, 1)
+    d_disp = [similar(d) for d in disps]
+    d_pose = temporal ? ROCArray{Float32}(undef, 6, 2n) : nothing
+    ws = ROCVector{UInt8}(undef, ccall((:md2_loss_sources_workspace_size, lib), Csize_t, (Ref{LossCfg}, Cint), cfg, nsrc))
+    out = LossOut(pointer(loss), C_NULL, ntuple(i -> i <= length(d_disp) ? pointer(d_disp[i]) : Ptr{Float32}(C_NULL), 5),
+                  temporal ? pointer(d_pose) : C_NULL, C_NULL, C_NULL, C_NULL, C_NULL)
+    dptrs = [pointer(d) for d in disps]
+    check(ccall((:md2_loss_fwd_bwd_sources, lib), Cint,
+                (Ref{LossCfg}, Cint, Ptr{LossSource}, Ptr{Float32}, Clonglong, Ptr{Ptr{Float32}}, Ptr{Float32},
+                 Ptr{Float32}, Cfloat, Ref{LossOut}, Ptr{UInt8}, Ptr{Cvoid}),
+                cfg, nsrc, src, pointer(x) + 4 * (target_id - 1) * fs, L * fs, dptrs, temporal ? pointer(pose) : C_NULL,
+                ptr(auto_loss), Float32(dloss), out, ws, stream_ptr()))
+    return loss, d_disp, d_pose
+end
+
 # Depth evaluation (Monodepth2 / Eigen protocol; include/md2.h states every step): disparities
 # disp (w,h,n) or (w,h,1,n) against ground-truth depth gt (Wg,Hg,n), one batched call, no host
 # sync.  crop: :garg, nothing (whole image) or 0-based half-open (y0, y1, x0, x1) in gt pixels.
@@ -903,6 +1010,19 @@ end
 
 # One whole step (forward, loss, backward, ADAM(η) with β = (0.9, 0.999), ϵ = 1e-8) replayed as a
 # captured hipGraph; the same kernels in the same order as train_loss + gradient! + update!
+# the captured step with stereo supervision (md2_model_train_step_graph_stereo; see train_loss_stereo)
+function train_step_graph_stereo!(m::HIPModel, x::ROCArray{Float32,5}, x_stereo::ROCArray{Float32,4},
+                                  stereo_Rt::ROCArray{Float32,2}, auto_loss, η; temporal::Bool=true, x_net=nothing)
+    m.packed || repack!(m)
+    m.step += 1; loss = ROCVector{Float32}(undef, 1)
+    check(ccall((:md2_model_train_step_graph_stereo, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float32},
+                 Ptr{Float32}, Ptr{Float32}, Cfloat, Cint, Ptr{Float32}, Ptr{Cvoid}),
+                m.handle, x, ptr(x_net), x_stereo, stereo_Rt, temporal ? 1 : 0, ptr(auto_loss), m.m, m.v, η,
+                m.step, loss, stream_ptr()))
+    return loss
+end
+
 function train_step_graph!(m::HIPModel, x::ROCArray{Float32,5}, auto_loss, η; x_net=nothing)
     m.packed || repack!(m)
     m.step += 1; loss = ROCVector{Float32}(undef, 1)

@@ -154,6 +154,51 @@ int md2_loss_fwd_bwd(const md2_loss_cfg* cfg, const float* const* disp, const fl
                        (hipStream_t)stream);
 }
 
+size_t md2_loss_sources_workspace_size(const md2_loss_cfg* cfg, int nsrc) {
+  if (!cfg) return 0;
+  return loss_tail_sources_workspace_bytes(to_tail_cfg(cfg), nsrc);
+}
+
+int md2_loss_fwd_bwd_sources(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
+                             const float* target, long long target_sample_stride,
+                             const float* const* disp, const float* pose, const float* automask,
+                             float dloss, const md2_loss_out* out, void* workspace, void* stream) {
+  MD2_CHECK_ARG(cfg != nullptr && out != nullptr && out->loss != nullptr, "cfg/out/loss");
+  MD2_CHECK_ARG(nsrc >= 1 && nsrc <= MD2_MAX_SOURCES, "nsrc must be 1, 2 or 3");
+  MD2_CHECK_ARG(sources != nullptr, "sources: null pointer");
+  LossSource src[MAX_SOURCES];
+  for (int s = 0; s < nsrc; ++s)
+    src[s] = LossSource{sources[s].frames, (long)sources[s].sample_stride, sources[s].pose_block,
+                        sources[s].invert, sources[s].Rt};
+  LossTailOut o{};
+  o.loss = out->loss;
+  o.terms = out->terms;
+  for (int s = 0; s < MAX_SCALES; ++s) o.d_disp[s] = out->d_disp[s];
+  o.d_pose = out->d_pose;
+  o.vis_loss = out->vis_loss;
+  o.vis_sel = out->vis_sel;
+  o.vis_warped = out->vis_warped;
+  o.vis_cell = out->vis_cell;
+  return loss_tail_sources_run(to_tail_cfg(cfg), nsrc, src, target, (long)target_sample_stride, disp,
+                               pose, automask, dloss, o, workspace, (hipStream_t)stream);
+}
+
+int md2_automasking_loss_sources(int nsrc, const md2_loss_source* sources, const float* target,
+                                 long long target_sample_stride, int n, int c, int h, int w,
+                                 float* out, void* stream) {
+  MD2_CHECK_ARG(nsrc >= 1 && nsrc <= MD2_MAX_SOURCES, "nsrc must be 1, 2 or 3");
+  MD2_CHECK_ARG(sources && target && out && n > 0 && w >= 2 && h >= 2, "automasking_loss_sources args");
+  const float* fr[MAX_SOURCES];
+  long ss[MAX_SOURCES];
+  for (int s = 0; s < nsrc; ++s) {
+    MD2_CHECK_ARG(sources[s].frames != nullptr, "source without frames");
+    fr[s] = sources[s].frames;
+    ss[s] = (long)sources[s].sample_stride;
+  }
+  return launch_automask_sources(target, (long)target_sample_stride, fr, ss, nsrc, n, c, h, w, out,
+                                 (hipStream_t)stream);
+}
+
 static WarpOpCfg to_warp_cfg(const md2_warp_cfg* c) {
   WarpOpCfg w{};
   w.N = c->n;
@@ -518,6 +563,23 @@ int md2_model_backward_segment(md2_model* m, int k, long long* off, long long* l
   if (off) *off = o;
   if (len) *len = l;
   return MD2_OK;
+}
+
+int md2_model_forward_loss_stereo(md2_model* m, const float* x, const float* x_net, const float* x_stereo,
+                                  const float* stereo_Rt, int temporal, const float* auto_loss, float* loss,
+                                  float* terms, void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_forward_loss_stereo(m->impl, x, x_net, x_stereo, stereo_Rt, temporal, auto_loss, loss, terms,
+                                   (hipStream_t)stream);
+}
+
+int md2_model_train_step_graph_stereo(md2_model* m, const float* x, const float* x_net, const float* x_stereo,
+                                      const float* stereo_Rt, int temporal, const float* auto_loss,
+                                      float* adam_m, float* adam_v, float lr, int step, float* loss,
+                                      void* stream) {
+  MD2_CHECK_ARG(m, "model");
+  return model_train_step_graph_stereo(m->impl, x, x_net, x_stereo, stereo_Rt, temporal, auto_loss, adam_m, adam_v,
+                                       lr, step, loss, (hipStream_t)stream);
 }
 
 int md2_model_adam(md2_model* m, float* adam_m, float* adam_v, float lr, float beta1,

@@ -52,6 +52,25 @@ struct PhotoArgs {
   int N;
 };
 
+// The photometric pass over 1..MAX_SOURCES sources, each with its own base pointer and sample
+// stride (photo_sources.hip).  In its scales, partials rows are 1 + 12 nsrc floats (loss sum, then
+// dR(9) dt(3) per source), sel_map holds 0..nsrc-1 or -1, and cell_map is [nsrc][N][H][W].
+constexpr int MAX_SOURCES = 3;
+struct PhotoSrcArgs {
+  PhotoScale sc[MAX_SCALES];
+  int nscales;
+  int nsrc;
+  const float* target;          // sample i's target frame at target + i * target_sample_stride
+  long target_sample_stride;
+  const float* src[MAX_SOURCES];
+  long src_sample_stride[MAX_SOURCES];
+  const float* Rt;              // [nsrc][N][12]
+  const float* automask;        // [N][H][W] or nullptr
+  float wloss;
+  const float* gmap;            // [N][H][W] per-pixel cotangent (times wloss) or nullptr
+  int N;
+};
+
 // Wave tiling of the photometric pass (photo.hip): 60 output columns x `rows` output rows per
 // wave, tiles_x * tiles_y tiles per sample and scale.
 struct PhotoTiling {
@@ -130,6 +149,22 @@ int launch_photometric(const PhotoArgs& a, const Geom& g, int C, hipStream_t st)
 // photometric_loss(source, target)
 int launch_automask(const float* x, long x_sample_stride, long x_frame_stride, int target,
                     int src0, int src1, int N, int C, int H, int W, float* out, hipStream_t st);
+// the same over a.nsrc sources (photo_sources.hip); the nsrc = 2 instance gives launch_photometric's
+// bits and is not on the two-source path
+int launch_photometric_sources(const PhotoSrcArgs& a, const Geom& g, int C, hipStream_t st);
+// min over nsrc raw sources (pointer + sample stride each, [C][H][W] frames) of
+// photometric_loss(source, target), first argmin on ties; two sources give launch_automask's bits
+int launch_automask_sources(const float* target, long target_sample_stride, const float* const* src,
+                            const long* src_sample_stride, int nsrc, int N, int C, int H, int W,
+                            float* out, hipStream_t st);
+// out [nsrc][N][C][H][W]
+int launch_warp_vis_sources(const PhotoSrcArgs& a, int scale, const Geom& g, int C, float* out,
+                            hipStream_t st);
+// launch_loss_finalize / launch_pose_grad_reduce over partials rows of 1 + 12 nsrc floats;
+// dRt [nsrc * N][12]
+int launch_loss_finalize_sources(const FinalizeArgs& a, int nsrc, float* dRt, float* loss,
+                                 hipStream_t st);
+int launch_pose_grad_reduce_sources(const FinalizeArgs& a, int nsrc, float* dRt, hipStream_t st);
 // warped sources only (train_loss vis_warped): out [2][N][C][H][W]
 int launch_warp_vis(const PhotoArgs& a, int scale, const Geom& g, int C, float* out, hipStream_t st);
 // partial rows per scale of the photometric pass run with `nscales` scales

@@ -184,6 +184,226 @@ int loss_tail_run(const LossTailCfg& c, const float* const* disp, const float* p
 
 
 // ---------------------------------------------------------------------------------------------
+// The sources form: loss_tail_run with the photometric pass, the reductions and the visualisation
+// warp over S sources (photo_sources.hip), learned or fixed.  Disparity sums, smoothness and the
+// upsample adjoint are the same launches.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct SrcLayout {
+  size_t Rt, dRt, Rtl, dRtl, g_full[MAX_SCALES], mean, photo[MAX_SCALES], smooth[MAX_SCALES],
+      tsum[MAX_SCALES], terms, total;
+};
+
+SrcLayout src_layout(const LossTailCfg& c, int S) {
+  SrcLayout L{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    size_t o = off;
+    off += align256(bytes);
+    return o;
+  };
+  L.Rt = take(sizeof(float) * S * c.N * 12);
+  L.dRt = take(sizeof(float) * S * c.N * 12);
+  L.Rtl = take(sizeof(float) * S * c.N * 12);    // learned sources only, in pose-block order
+  L.dRtl = take(sizeof(float) * S * c.N * 12);
+  L.mean = take(sizeof(double) * (size_t)c.nscales * c.N * MEAN_PARTS);
+  for (int s = 0; s < c.nscales; ++s) {
+    L.g_full[s] = take(sizeof(float) * (size_t)c.N * c.W * c.H);
+    L.photo[s] = take(sizeof(float) * (1 + 12 * S) * photometric_blocks(c.W, c.H, c.N, c.nscales));
+    L.smooth[s] = take(sizeof(float) * 2 * smooth_blocks(c.W, c.H, c.N));
+    L.tsum[s] = take(sizeof(double) * smooth_blocks(c.W, c.H, c.N));
+  }
+  L.terms = take(sizeof(float) * 2 * MAX_SCALES);
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+size_t loss_tail_sources_workspace_bytes(const LossTailCfg& c, int nsrc) {
+  if (nsrc < 1 || nsrc > MAX_SOURCES) return 0;
+  return src_layout(c, nsrc).total;
+}
+
+int loss_tail_sources_run(const LossTailCfg& c, int S, const LossSource* src, const float* target,
+                          long target_sample_stride, const float* const* disp, const float* pose,
+                          const float* automask, float dloss, const LossTailOut& o, void* workspace,
+                          hipStream_t st) {
+  MD2_CHECK_ARG(S >= 1 && S <= MAX_SOURCES, "nsrc must be 1, 2 or 3");
+  MD2_CHECK_ARG(src != nullptr, "sources: null pointer");
+  MD2_CHECK_ARG(c.N > 0 && c.W > 2 && c.H > 2, "loss tail dims");
+  MD2_CHECK_ARG(c.nscales >= 1 && c.nscales <= MAX_SCALES, "nscales");
+  MD2_CHECK_ARG(c.C == 1 || c.C == 3, "channels must be 1 or 3");
+  MD2_CHECK_ARG(workspace != nullptr && disp != nullptr && target != nullptr, "null pointer");
+  // the learned sources' blocks of `pose` are 0..n_learned-1, each once
+  int n_learned = 0, seen = 0, invert_mask = 0;
+  for (int s = 0; s < S; ++s) {
+    MD2_CHECK_ARG(src[s].frames != nullptr, "source without frames");
+    if (src[s].pose_block >= 0) {
+      MD2_CHECK_ARG(pose != nullptr, "a learned source needs pose");
+      MD2_CHECK_ARG(src[s].pose_block < S && !((seen >> src[s].pose_block) & 1),
+                    "pose_block must be distinct and below the number of learned sources");
+      seen |= 1 << src[s].pose_block;
+      if (src[s].invert) invert_mask |= 1 << src[s].pose_block;
+      ++n_learned;
+    } else {
+      MD2_CHECK_ARG(src[s].pose_block == -1, "pose_block must be >= 0 (learned) or -1 (fixed)");
+      MD2_CHECK_ARG(src[s].Rt != nullptr, "a fixed source needs Rt");
+    }
+  }
+  MD2_CHECK_ARG(seen == (1 << n_learned) - 1,
+                "pose_block must be distinct and below the number of learned sources");
+  for (int s = 0; s < c.nscales; ++s)
+    MD2_CHECK_ARG(c.dw[s] >= 1 && c.dh[s] >= 1 && c.dw[s] <= c.W && c.dh[s] <= c.H, "scale dims");
+
+  float* loss = o.loss;
+  const float* const* d_disp = o.d_disp;
+  float* d_pose = n_learned > 0 ? o.d_pose : nullptr;
+  const SrcLayout L = src_layout(c, S);
+  char* ws = (char*)workspace;
+  float* Rt = (float*)(ws + L.Rt);
+  float* dRt = (float*)(ws + L.dRt);
+  float* Rtl = (float*)(ws + L.Rtl);
+  float* dRtl = (float*)(ws + L.dRtl);
+  double* mean = (double*)(ws + L.mean);
+  float* tterms = o.terms ? o.terms : (float*)(ws + L.terms);
+
+  Geom g;
+  std::memcpy(g.K, c.K, sizeof(g.K));
+  std::memcpy(g.invK, c.invK, sizeof(g.invK));
+  g.min_disp = (float)(1.0 / c.max_depth);
+  g.disp_range = (float)(1.0 / c.min_depth - 1.0 / c.max_depth);
+  g.W = c.W;
+  g.H = c.H;
+  g.wm1 = (float)(c.W - 1);
+  g.hm1 = (float)(c.H - 1);
+
+  // Rt [S][N][12]: learned rows from composeT (in pose-block order, then copied to the source's
+  // place), fixed rows from the caller
+  const size_t rt_bytes = sizeof(float) * c.N * 12;
+  if (n_learned > 0) MD2_TRY(launch_so3_fwd(pose, n_learned * c.N, c.N, invert_mask, Rtl, st));
+  for (int s = 0; s < S; ++s) {
+    const float* from = src[s].pose_block >= 0 ? Rtl + (size_t)src[s].pose_block * c.N * 12 : src[s].Rt;
+    MD2_HIP(hipMemcpyAsync(Rt + (size_t)s * c.N * 12, from, rt_bytes, hipMemcpyDeviceToDevice, st));
+  }
+
+  const float up = dloss / c.divisor;
+  const long photo_blk = photometric_blocks(c.W, c.H, c.N, c.nscales);
+  const long smooth_blk = smooth_blocks(c.W, c.H, c.N);
+  FinalizeArgs fa{};
+  fa.nscales = c.nscales;
+  fa.N = c.N;
+  fa.photo_scale = 1.f / ((float)c.N * c.W * c.H);
+  fa.terms = tterms;
+  fa.divisor = c.divisor;
+
+  PhotoSrcArgs pa{};
+  pa.nscales = c.nscales;
+  pa.nsrc = S;
+  pa.target = target;
+  pa.target_sample_stride = target_sample_stride;
+  for (int s = 0; s < S; ++s) {
+    pa.src[s] = src[s].frames;
+    pa.src_sample_stride[s] = src[s].sample_stride;
+  }
+  pa.Rt = Rt;
+  pa.automask = automask;
+  pa.wloss = up / ((float)c.N * c.W * c.H);
+  pa.N = c.N;
+  const size_t plane = (size_t)c.N * c.W * c.H;
+  DispSumBatch db{};
+  db.W = c.W;
+  db.H = c.H;
+  db.N = c.N;
+  db.parts = MEAN_PARTS;
+  for (int s = 0; s < c.nscales; ++s) {
+    PhotoScale& ps = pa.sc[s];
+    ps.disp = disp[s];
+    ps.dw = c.dw[s];
+    ps.dh = c.dh[s];
+    ps.rx = ratio(c.dw[s], c.W);
+    ps.ry = ratio(c.dh[s], c.H);
+    ps.g_disp = (float*)(ws + L.g_full[s]);
+    ps.partials = (float*)(ws + L.photo[s]);
+    ps.loss_map = o.vis_loss ? o.vis_loss + s * plane : nullptr;
+    ps.sel_map = o.vis_sel ? o.vis_sel + s * plane : nullptr;
+    ps.cell_map = o.vis_cell ? o.vis_cell + (size_t)S * s * plane : nullptr;
+    db.s[s] = DispSumArgs{disp[s], c.dw[s], c.dh[s], ps.rx, ps.ry, mean + (size_t)s * c.N * MEAN_PARTS};
+  }
+  MD2_TRY(launch_disp_sum(db, c.nscales, st));
+  if (o.photo_events) MD2_HIP(hipEventRecord(o.photo_events[0], st));
+  MD2_TRY(launch_photometric_sources(pa, g, c.C, st));
+  if (o.photo_events) MD2_HIP(hipEventRecord(o.photo_events[1], st));
+  if (o.vis_warped) MD2_TRY(launch_warp_vis_sources(pa, c.nscales - 1, g, c.C, o.vis_warped, st));
+
+  SmoothArgs sas[MAX_SCALES];
+  UpAdjArgs uas[MAX_SCALES];
+  int nua = 0;
+  for (int s = 0; s < c.nscales; ++s) {
+    const PhotoScale& ps = pa.sc[s];
+    double* mp = mean + (size_t)s * c.N * MEAN_PARTS;
+    float* sp = (float*)(ws + L.smooth[s]);
+    double* tp = (double*)(ws + L.tsum[s]);
+    SmoothArgs& sa = sas[s];
+    sa = SmoothArgs{};
+    sa.disp = disp[s];
+    sa.dw = c.dw[s];
+    sa.dh = c.dh[s];
+    sa.rx = ps.rx;
+    sa.ry = ps.ry;
+    sa.img = target;
+    sa.img_sample_stride = target_sample_stride;
+    sa.mean_partials = c.smooth_normalize ? mp : nullptr;
+    sa.mean_parts = c.smooth_normalize ? MEAN_PARTS : 0;
+    sa.ws = up * c.smooth_w[s];
+    sa.g_disp = ps.g_disp;
+    sa.partials = sp;
+    sa.tsum = c.smooth_normalize ? tp : nullptr;
+    sa.N = c.N;
+    sa.W = c.W;
+    sa.H = c.H;
+
+    UpAdjArgs ua{};
+    ua.g_full = ps.g_disp;
+    ua.disp = disp[s];
+    ua.dw = c.dw[s];
+    ua.dh = c.dh[s];
+    ua.rx = ps.rx;
+    ua.ry = ps.ry;
+    ua.mean_partials = mp;
+    ua.mean_parts = MEAN_PARTS;
+    ua.smooth_tsum = c.smooth_normalize ? tp : nullptr;
+    ua.smooth_parts = (int)(smooth_blk / c.N);
+    ua.ws = sa.ws;
+    ua.sigmoid = c.sigmoid_grad;
+    ua.accumulate = 0;
+    ua.out = (float*)d_disp[s];
+    ua.N = c.N;
+    ua.W = c.W;
+    ua.H = c.H;
+    if (d_disp[s]) uas[nua++] = ua;
+
+    fa.photo_partials[s] = ps.partials;
+    fa.photo_blocks[s] = photo_blk;
+    fa.smooth_partials[s] = sp;
+    fa.smooth_blocks[s] = smooth_blk;
+    fa.smooth_scale[s] = c.smooth_w[s];
+  }
+  MD2_TRY(launch_smooth(sas, c.nscales, c.C, st));
+  if (nua > 0) MD2_TRY(launch_up_adjoint(uas, nua, st));
+  MD2_TRY(launch_loss_finalize_sources(fa, S, d_pose ? dRt : nullptr, loss, st));
+  if (d_pose) {
+    // only the learned sources are differentiated: their dRt rows, in pose-block order
+    for (int s = 0; s < S; ++s)
+      if (src[s].pose_block >= 0)
+        MD2_HIP(hipMemcpyAsync(dRtl + (size_t)src[s].pose_block * c.N * 12, dRt + (size_t)s * c.N * 12,
+                               rt_bytes, hipMemcpyDeviceToDevice, st));
+    MD2_TRY(launch_so3_bwd(pose, n_learned * c.N, c.N, invert_mask, dRtl, d_pose, 0, st));
+  }
+  return MD2_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------
 // Op-level warp + photometric loss of ONE scale (src/training.jl:43-62): upsample the disparity,
 // depth, backproject, project with each composed pose, border grid_sample, SSIM + L1, min over
 // the two sources (and the automask).  Forward: the per-pixel warp_loss map; pullback: from a

@@ -42,6 +42,25 @@ int loss_tail_run(const LossTailCfg& c, const float* const* disp, const float* p
                   const float* x, const float* automask, float dloss, const LossTailOut& o,
                   void* workspace, hipStream_t st);
 
+// The loss tail over 1..MAX_SOURCES sources, each LEARNED (its pose comes from the pose network
+// and gets a gradient) or FIXED (a caller-supplied transform, data).  c.target / src0 / src1 /
+// invert_mask / x_*_stride are not read.
+struct LossSource {
+  const float* frames;        // sample i's [C][H][W] frame at frames + i * sample_stride
+  long sample_stride;
+  int pose_block;             // >= 0: learned, poses at rows pose[pose_block * N + i]; -1: fixed
+  int invert;                 // learned: composeT's inverse transform
+  const float* Rt;            // fixed: device [N][12] (R row-major, t)
+};
+size_t loss_tail_sources_workspace_bytes(const LossTailCfg& c, int nsrc);
+// pose: [n_learned * N][6] (may be nullptr without learned sources); o.d_pose [n_learned * N][6],
+// rows as in pose; o.vis_warped [nsrc][N][C][H][W]; o.vis_cell [nscales][nsrc][N][H][W];
+// o.vis_sel holds 0..nsrc-1 or -1.  The learned sources' pose blocks must be 0..n_learned-1, each once.
+int loss_tail_sources_run(const LossTailCfg& c, int nsrc, const LossSource* src, const float* target,
+                          long target_sample_stride, const float* const* disp, const float* pose,
+                          const float* automask, float dloss, const LossTailOut& o, void* workspace,
+                          hipStream_t st);
+
 // Op-level per-scale warp + photometric loss (md2_warp_photometric_*).
 struct WarpOpCfg {
   int N, C, W, H, dw, dh;

@@ -72,6 +72,32 @@ int model_forward_loss_aug(Model* m, const float* x, const float* x_net, const f
   return m->forward_loss(x, x_net, automask, loss, terms, st);
 }
 
+static int check_stereo_args(const Model* m, const float* x_stereo, const float* stereo_Rt, int temporal,
+                             const char* what) {
+  if (m->E > 0) {
+    set_error(std::string(what) + ": stereo supervision is not supported in MPI mode (embedding_levels > 0)");
+    return MD2_ENOTSUP;
+  }
+  MD2_CHECK_ARG(x_stereo && stereo_Rt, "x_stereo / stereo_Rt");
+  MD2_CHECK_ARG(temporal == 0 || temporal == 1, "temporal must be 0 (S) or 1 (MS)");
+  return MD2_OK;
+}
+
+int model_forward_loss_stereo(Model* m, const float* x, const float* x_net, const float* x_stereo,
+                              const float* stereo_Rt, int temporal, const float* automask, float* loss,
+                              float* terms, hipStream_t st) {
+  MD2_CHECK_ARG(m && x, "model/x");
+  MD2_TRY(refuse_testmode(m, "forward_loss_stereo"));
+  MD2_TRY(check_stereo_args(m, x_stereo, stereo_Rt, temporal, "forward_loss_stereo"));
+  if (!x_net) x_net = x;
+  MD2_TRY(m->ensure_stereo_ws());
+  MD2_TRY(m->adam_join(st));
+  m->cur_x = x_net;
+  m->cot_ready = 1;
+  const StereoIn si{x_stereo, stereo_Rt, temporal};
+  return m->forward_loss(x, x_net, automask, loss, terms, st, &si);
+}
+
 int model_forward_loss(Model* m, const float* x, const float* automask, float* loss, float* terms,
                        hipStream_t st) {
   return model_forward_loss_aug(m, x, nullptr, automask, loss, terms, st);
@@ -108,7 +134,8 @@ int model_num_segments(Model* m) { return m ? 6 : 0; }
 // executor's input buffers, replays
 // on `st`, and copies the loss out.  ADAM's step count lives on the device (adam_prep), re-set
 // only when the caller's `step` is not the one the graph expects next.
-static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, float* adam_v, float lr) {
+static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, float* adam_v, float lr,
+                        int stereo_mode = 0) {
   auto& g = m->g;
   if (g.exec) {
     MD2_HIP(hipGraphExecDestroy(g.exec));
@@ -126,11 +153,18 @@ static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, 
   if (with_net && !g.x_net)
     MD2_TRY(m->alloc(&g.x_net, (long)m->N * 3 * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W));
   const float* net = with_net ? g.x_net : g.x;
+  if (stereo_mode && !g.x_stereo) {
+    MD2_TRY(m->alloc(&g.x_stereo, (long)m->N * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W));
+    MD2_TRY(m->alloc(&g.stereo_Rt, (long)m->N * 12));
+  }
+  if (stereo_mode) MD2_TRY(m->ensure_stereo_ws());
+  const StereoIn si{g.x_stereo, g.stereo_Rt, stereo_mode == 1 ? 1 : 0};
   MD2_HIP(hipStreamBeginCapture(g.st, hipStreamCaptureModeThreadLocal));
   auto body = [&]() -> int {
     m->cur_x = net;
     m->cot_ready = 1;
-    MD2_TRY(m->forward_loss(g.x, net, with_auto ? g.autoloss : nullptr, g.loss, nullptr, g.st));
+    MD2_TRY(m->forward_loss(g.x, net, with_auto ? g.autoloss : nullptr, g.loss, nullptr, g.st,
+                            stereo_mode ? &si : nullptr));
     for (int k = 0; k < model_num_segments(m); ++k) MD2_TRY(model_backward_segment(m, k, nullptr, nullptr, g.st));
     // the step counter advances whether or not the guard lets the update through (md2.h)
     MD2_TRY(adam_prep(g.step, g.bc, 0.9f, 0.999f, g.st));
@@ -160,14 +194,17 @@ static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, 
   g.lr = lr;
   g.with_auto = with_auto ? 1 : 0;
   g.with_net = with_net ? 1 : 0;
+  g.stereo_mode = stereo_mode;
   g.guard_on = m->gd.on ? 1 : 0;
   g.guard_max = m->gd.max_norm;
   g.next_step = -1;
   return MD2_OK;
 }
 
-int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, const float* auto_loss,
-                               float* adam_m, float* adam_v, float lr, int step, float* loss, hipStream_t st) {
+// stereo_mode 0: x_stereo / stereo_Rt are not read (train_step_graph, _aug); 1 MS, 2 S
+static int train_step_graph_impl(Model* m, const float* x, const float* x_net, const float* x_stereo,
+                                 const float* stereo_Rt, int stereo_mode, const float* auto_loss, float* adam_m,
+                                 float* adam_v, float lr, int step, float* loss, hipStream_t st) {
   MD2_CHECK_ARG(m && x && adam_m && adam_v && loss && step >= 1, "train_step_graph args");
   MD2_TRY(refuse_testmode(m, "train_step_graph"));
   MD2_TRY(refuse_mpi_net(m, x_net, "train_step_graph_aug"));
@@ -176,6 +213,10 @@ int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, con
   const bool with_auto = auto_loss != nullptr;
   const bool with_net = x_net != nullptr;
   if (m->pf.on) {   // per-launch HIP events cannot live in a replayed graph: eager step
+    if (stereo_mode)
+      MD2_TRY(model_forward_loss_stereo(m, x, x_net, x_stereo, stereo_Rt, stereo_mode == 1, auto_loss, loss,
+                                        nullptr, st));
+    else
     MD2_TRY(model_forward_loss_aug(m, x, x_net, auto_loss, loss, nullptr, st));
     for (int k = 0; k < model_num_segments(m); ++k) MD2_TRY(model_backward_segment(m, k, nullptr, nullptr, st));
     return model_adam(m, adam_m, adam_v, lr, 0.9f, 0.999f, 1e-8f, step, 1.f, st);
@@ -184,12 +225,16 @@ int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, con
   // pending per-segment updates (outside the capture: the event lives outside the graph)
   MD2_TRY(m->adam_join(st));
   if (!g.exec || g.adam_m != adam_m || g.adam_v != adam_v || g.lr != lr || g.with_auto != (int)with_auto ||
-      g.with_net != (int)with_net || g.guard_on != (int)m->gd.on ||
+      g.with_net != (int)with_net || g.stereo_mode != stereo_mode || g.guard_on != (int)m->gd.on ||
       (m->gd.on && g.guard_max != m->gd.max_norm))
-    MD2_TRY(capture_step(m, with_auto, with_net, adam_m, adam_v, lr));
+    MD2_TRY(capture_step(m, with_auto, with_net, adam_m, adam_v, lr, stereo_mode));
   const size_t xb = sizeof(float) * (size_t)m->N * 3 * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W;
   if (x != g.x) MD2_HIP(hipMemcpyAsync(g.x, x, xb, hipMemcpyDeviceToDevice, st));
   if (with_net && x_net != g.x_net) MD2_HIP(hipMemcpyAsync(g.x_net, x_net, xb, hipMemcpyDeviceToDevice, st));
+  if (stereo_mode) {
+    MD2_HIP(hipMemcpyAsync(g.x_stereo, x_stereo, xb / 3, hipMemcpyDeviceToDevice, st));
+    MD2_HIP(hipMemcpyAsync(g.stereo_Rt, stereo_Rt, sizeof(float) * (size_t)m->N * 12, hipMemcpyDeviceToDevice, st));
+  }
   if (with_auto)
     MD2_HIP(hipMemcpyAsync(g.autoloss, auto_loss, sizeof(float) * (size_t)m->N * m->cfg.H * m->cfg.W,
                            hipMemcpyDeviceToDevice, st));
@@ -200,6 +245,20 @@ int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, con
   m->cot_ready = 1;
   g.next_step = step + 1;
   return MD2_OK;
+}
+
+int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, const float* auto_loss,
+                               float* adam_m, float* adam_v, float lr, int step, float* loss, hipStream_t st) {
+  return train_step_graph_impl(m, x, x_net, nullptr, nullptr, 0, auto_loss, adam_m, adam_v, lr, step, loss, st);
+}
+
+int model_train_step_graph_stereo(Model* m, const float* x, const float* x_net, const float* x_stereo,
+                                  const float* stereo_Rt, int temporal, const float* auto_loss, float* adam_m,
+                                  float* adam_v, float lr, int step, float* loss, hipStream_t st) {
+  MD2_CHECK_ARG(m, "model");
+  MD2_TRY(check_stereo_args(m, x_stereo, stereo_Rt, temporal, "train_step_graph_stereo"));
+  return train_step_graph_impl(m, x, x_net, x_stereo, stereo_Rt, temporal ? 1 : 2, auto_loss, adam_m, adam_v, lr,
+                               step, loss, st);
 }
 
 int model_train_step_graph(Model* m, const float* x, const float* auto_loss, float* adam_m,

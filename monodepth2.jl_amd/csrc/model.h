@@ -63,6 +63,14 @@ int model_forward_loss(Model* m, const float* x, const float* automask, float* l
 // the automask and the loss tail read x; x_net == nullptr or == x is model_forward_loss
 int model_forward_loss_aug(Model* m, const float* x, const float* x_net, const float* automask, float* loss,
                            float* terms, hipStream_t st);
+// stereo supervision: x_stereo [N][C][H][W] (the other camera at the target's time) with its fixed
+// transform stereo_Rt [N][12]; temporal = 1: the loss over (src0, src1, stereo), 0: stereo alone
+int model_forward_loss_stereo(Model* m, const float* x, const float* x_net, const float* x_stereo,
+                              const float* stereo_Rt, int temporal, const float* automask, float* loss,
+                              float* terms, hipStream_t st);
+int model_train_step_graph_stereo(Model* m, const float* x, const float* x_net, const float* x_stereo,
+                                  const float* stereo_Rt, int temporal, const float* auto_loss, float* adam_m,
+                                  float* adam_v, float lr, int step, float* loss, hipStream_t st);
 // forward only ((m)(x, source_ids, target_id), src/model.jl:31-55): outputs via model_outputs;
 // a backward after it needs model_set_cotangents
 int model_forward(Model* m, const float* x, hipStream_t st);

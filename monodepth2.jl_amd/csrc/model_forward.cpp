@@ -346,8 +346,19 @@ int Model::forward(const float* x, hipStream_t st) {
 }
 
 // x_net feeds the networks; the automask and the loss tail read x (x_net == x: the plain step)
+int Model::ensure_stereo_ws() {
+  if (tail_src_ws) return MD2_OK;
+  float* q;
+  MD2_TRY(alloc(&q, loss_tail_sources_workspace_bytes(tail, MAX_SOURCES) / sizeof(float) + 64));
+  tail_src_ws = q;
+  if (!amask) MD2_TRY(alloc(&amask, (long)N * cfg.H * cfg.W));
+  return MD2_OK;
+}
+
+// stereo: the loss tail and the automask run over (src0, src1, stereo frame) -- MS -- or over the
+// stereo frame alone -- S, where the pose network's cotangent is zero; the networks never see it
 int Model::forward_loss(const float* x, const float* x_net, const float* automask, float* loss, float* terms,
-                        hipStream_t st) {
+                        hipStream_t st, const StereoIn* stereo) {
   MD2_TRY(forward(x_net, st));
   const float* disps[MAX_SCALES] = {};
   LossTailOut o{};
@@ -362,6 +373,37 @@ int Model::forward_loss(const float* x, const float* x_net, const float* automas
   if (pf.on) {
     for (int k = 0; k < 2; ++k) pev[k] = pf.ev();
     o.photo_events = pev;
+  }
+  if (stereo) {
+    const long fs = tail.x_frame_stride, ss = tail.x_sample_stride;
+    LossSource src[MAX_SOURCES];
+    int S = 0;
+    if (stereo->temporal) {
+      src[S++] = LossSource{x + tail.src0 * fs, ss, 0, tail.invert_mask & 1, nullptr};
+      src[S++] = LossSource{x + tail.src1 * fs, ss, 1, (tail.invert_mask >> 1) & 1, nullptr};
+    }
+    src[S++] = LossSource{stereo->x, fs, -1, 0, stereo->Rt};
+    const float* target = x + tail.target * fs;
+    if (cfg.automask && !automask) {   // over the same sources the loss uses
+      const float* fr[MAX_SOURCES];
+      long fss[MAX_SOURCES];
+      for (int s = 0; s < S; ++s) {
+        fr[s] = src[s].frames;
+        fss[s] = src[s].sample_stride;
+      }
+      MD2_TRY(launch_automask_sources(target, ss, fr, fss, S, N, cfg.arch.in_ch, cfg.H, cfg.W, amask, st));
+      automask = amask;
+    }
+    // S: no learned source, so the tail writes no d_pose; the pose network still runs its backward
+    // (the segments, the DP buckets and the graph keep their shape) on a zero cotangent
+    if (!stereo->temporal) MD2_HIP(hipMemsetAsync(d_pose, 0, sizeof(float) * 2 * N * 6, st));
+    MD2_TRY(loss_tail_sources_run(tail, S, src, target, ss, disps, pose, cfg.automask ? automask : nullptr, 1.f,
+                                  o, tail_src_ws, st));
+    if (pf.on) {
+      const double bytes = (double)tail.nscales * ND * cfg.H * cfg.W * (8.0 + 4.0 * (1 + S) * cfg.arch.in_ch);
+      pf.recs.push_back({pev[0], pev[1], PROF_PHOTO, bytes, "photometric over sources (all scales)"});
+    }
+    return MD2_OK;
   }
   if (cfg.automask && !automask) {
     // automasking_loss(ssim, x, target; source_ids) (src/training.jl:9-11): identity

@@ -201,6 +201,8 @@ struct StepGraph {
   hipGraphExec_t exec = nullptr;
   hipStream_t st = nullptr;
   float *x = nullptr, *x_net = nullptr, *autoloss = nullptr, *loss = nullptr, *bc = nullptr;
+  float *x_stereo = nullptr, *stereo_Rt = nullptr;   // train_step_graph_stereo's input copies
+  int stereo_mode = -1;   // part of the capture: 0 no stereo source, 1 MS (temporal), 2 S
   int* step = nullptr;
   float *adam_m = nullptr, *adam_v = nullptr;
   float lr = 0.f;
@@ -209,6 +211,15 @@ struct StepGraph {
   int guard_on = -1;   // the gradient guard and its max_norm are part of the capture too
   float guard_max = 0.f;
   int next_step = -1;
+};
+
+// The stereo source of one forward_loss (md2_model_forward_loss_stereo): the partner camera's frame
+// x [N][C][H][W], its fixed transform Rt [N][12], and whether the temporal sources take part (MS) or
+// not (S).  Only the loss tail and the automask read it.
+struct StereoIn {
+  const float* x;
+  const float* Rt;
+  int temporal;
 };
 
 // Gradient guard (md2_model_set_grad_guard): between the backward and ADAM, grad_norm over the whole
@@ -287,6 +298,8 @@ class Model {
   float* pin = nullptr;
   float* hws = nullptr;         // the DepthDecoder's disparity heads run as one batch per pass (head.h)
   void* tail_ws = nullptr;
+  void* tail_src_ws = nullptr;  // the sources form's workspace (3 sources), allocated at first use
+  int ensure_stereo_ws();
   float* loss_buf = nullptr;
   float* amask = nullptr;       // automasking_loss of the current batch when the caller passes none
   // Running statistics of every BatchNorm in ONE flat vector (the layout of
@@ -378,7 +391,7 @@ class Model {
   int eval_pose(const TensorIn& in, int n, hipStream_t st);
   int forward(const float* x, hipStream_t st);
   int forward_loss(const float* x, const float* x_net, const float* automask, float* loss, float* terms,
-                   hipStream_t st);
+                   hipStream_t st, const StereoIn* stereo = nullptr);
 
   // ---- backward (model_backward.cpp)
   int conv_w(RConv& c, int nimg, const TensorIn& in, const float* dy, hipStream_t st);

@@ -138,6 +138,51 @@ __global__ __launch_bounds__(256) void automask_kernel(const float* __restrict__
   out[((long)n * H + gy) * W + gx] = l[1] < l[0] ? l[1] : l[0];   // first argmin on ties
 }
 
+// the same over S raw sources, each its own tensor (pointer + sample stride); S = 2 repeats
+// automask_kernel's arithmetic
+struct AutomaskSrc {
+  const float* src[MAX_SOURCES];
+  long ss[MAX_SOURCES];
+};
+template <int C, int S>
+__global__ __launch_bounds__(256) void automask_sources_kernel(const float* __restrict__ target,
+                                                               long t_ss, AutomaskSrc a, int W, int H,
+                                                               float* __restrict__ out) {
+  constexpr int RW = OT_W + 2, RH = OT_H + 2, NR = RW * RH;
+  __shared__ float s_t[C][NR], s_s[S][C][NR];
+  const int n = blockIdx.z, x0 = blockIdx.x * OT_W, y0 = blockIdx.y * OT_H;
+  const long HW = (long)W * H;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    load_region<1>(target + (long)n * t_ss + c * HW, W, H, x0, y0, s_t[c]);
+#pragma unroll
+    for (int s = 0; s < S; ++s) load_region<1>(a.src[s] + (long)n * a.ss[s] + c * HW, W, H, x0, y0, s_s[s][c]);
+  }
+  __syncthreads();
+  const int tx = threadIdx.x % OT_W, ty = threadIdx.x / OT_W;
+  const int gx = x0 + tx, gy = y0 + ty;
+  if (gx >= W || gy >= H) return;
+  int wi[9];
+  window_idx<1>(gx, gy, W, H, x0, y0, wi);
+  const int ci = (ty + 1) * RW + tx + 1;
+  float l[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    float ss = 0.f, l1 = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const SsimWin w = ssim_window(s_s[s][c], s_t[c], wi, ci);
+      ss += fminf(fmaxf(w.val, 0.f), 1.f);
+      l1 += fabsf(s_t[c][ci] - s_s[s][c][ci]);
+    }
+    l[s] = 0.85f * (ss / (float)C) + 0.15f * (l1 / (float)C);
+  }
+  float lmin = l[0];
+#pragma unroll
+  for (int s = 1; s < S; ++s) lmin = l[s] < lmin ? l[s] : lmin;   // first argmin on ties
+  out[((long)n * H + gy) * W + gx] = lmin;
+}
+
 // ---------------------------------------------------------------------------------------------
 // SSIM()(x, y) per channel plane, and its pullback to both arguments.
 // ---------------------------------------------------------------------------------------------
@@ -450,6 +495,43 @@ int launch_automask(const float* x, long x_sample_stride, long x_frame_stride, i
   else if (C == 1)
     hipLaunchKernelGGL(automask_kernel<1>, grid, dim3(256), 0, st, x, x_sample_stride,
                        x_frame_stride, target, src0, src1, W, H, out);
+  else {
+    set_error("automask: channels must be 1 or 3");
+    return MD2_ENOTSUP;
+  }
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
+namespace {
+template <int C>
+void automask_sources_c(const float* target, long t_ss, const AutomaskSrc& a, int nsrc, dim3 grid,
+                        int W, int H, float* out, hipStream_t st) {
+  if (nsrc == 1)
+    hipLaunchKernelGGL((automask_sources_kernel<C, 1>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
+  else if (nsrc == 2)
+    hipLaunchKernelGGL((automask_sources_kernel<C, 2>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
+  else
+    hipLaunchKernelGGL((automask_sources_kernel<C, 3>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
+}
+}  // namespace
+
+int launch_automask_sources(const float* target, long target_sample_stride, const float* const* src,
+                            const long* src_sample_stride, int nsrc, int N, int C, int H, int W,
+                            float* out, hipStream_t st) {
+  MD2_CHECK_ARG(nsrc >= 1 && nsrc <= MAX_SOURCES, "automask: 1 to 3 sources");
+  MD2_CHECK_ARG(target && src && out && N > 0 && W >= 2 && H >= 2, "automask args");
+  AutomaskSrc a{};
+  for (int s = 0; s < nsrc; ++s) {
+    MD2_CHECK_ARG(src[s] != nullptr, "automask: null source");
+    a.src[s] = src[s];
+    a.ss[s] = src_sample_stride[s];
+  }
+  const dim3 grid(cdiv(W, OT_W), cdiv(H, OT_H), N);
+  if (C == 3)
+    automask_sources_c<3>(target, target_sample_stride, a, nsrc, grid, W, H, out, st);
+  else if (C == 1)
+    automask_sources_c<1>(target, target_sample_stride, a, nsrc, grid, W, H, out, st);
   else {
     set_error("automask: channels must be 1 or 3");
     return MD2_ENOTSUP;

@@ -5,7 +5,8 @@ Host-side mirror of the reference's Julia API (``Params``, ``TrainCache``, ``Mod
 ``ADAM``) over the C-ABI of ``libmd2hip.so`` (include/md2.h).  There is no CPU fallback: every
 op runs the HIP kernels and a missing library raises."""
 from ._lib import MD2Error, lib  # noqa: F401
-from .loss import Params, TrainCache, depth10k_intrinsics, loss_tail, pack_poses  # noqa: F401
+from .loss import (Params, TrainCache, depth10k_intrinsics, loss_tail, pack_poses,  # noqa: F401
+                   stereo_transforms)
 from .model import (ADAM, DepthDecoder, Model, Pose, PoseDecoder, ResidualNetwork, ResNet,  # noqa: F401
                     decode_guard_state, disparity_bins, eval_disparity, eval_pose, flux_params, grad_norm, gradient, param_table,
                     pullback, set_flux_params, train_loss, train_step)
@@ -21,7 +22,7 @@ from .lidar import (kitti_odometry_velo_to_image, kitti_raw_velo_to_image, lidar
 from .color import JITTER_DTYPE, ColorJitter, color_jitter, jitter_params  # noqa: F401
 from .resize import decode_frames, load_frames, resize_frames  # noqa: F401
 
-__all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_poses", "lib", "MD2Error",
+__all__ = ["Params", "TrainCache", "depth10k_intrinsics", "loss_tail", "pack_poses", "stereo_transforms", "lib", "MD2Error",
            "ADAM", "DepthDecoder", "Model", "Pose", "PoseDecoder", "ResidualNetwork", "ResNet",
            "disparity_bins", "eval_disparity", "flux_params", "gradient", "param_table", "pullback", "set_flux_params", "train_loss",
            "train_step",

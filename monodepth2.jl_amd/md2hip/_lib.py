@@ -40,6 +40,15 @@ class LossOut(C.Structure):
     ]
 
 
+MAX_SOURCES = 3          # include/md2.h MD2_MAX_SOURCES
+
+
+class LossSource(C.Structure):
+    """``md2_loss_source``."""
+    _fields_ = [("frames", C.c_void_p), ("sample_stride", C.c_longlong), ("pose_block", C.c_int),
+                ("invert", C.c_int), ("Rt", C.c_void_p)]
+
+
 class ConvDesc(C.Structure):
     """``md2_conv_desc``."""
     _fields_ = [(n, C.c_int) for n in ("n", "cin", "h", "w", "cout", "kh", "kw", "stride", "pad",
@@ -278,11 +287,23 @@ _SIGS = {
     "md2_warp_photometric_workspace_size": (C.c_size_t, [C.POINTER(WarpCfg)]),
     "md2_warp_photometric_fwd": (C.c_int, [C.POINTER(WarpCfg), P, P, P, P, P, P, P, P]),
     "md2_warp_photometric_bwd": (C.c_int, [C.POINTER(WarpCfg), P, P, P, P, P, P, P, P, P]),
+    "md2_loss_sources_workspace_size": (C.c_size_t, [C.POINTER(LossCfg), C.c_int]),
+    "md2_loss_fwd_bwd_sources": (C.c_int, [C.POINTER(LossCfg), C.c_int, C.POINTER(LossSource), P, C.c_longlong,
+                                           FP, P, P, C.c_float, C.POINTER(LossOut), P, P]),
+    "md2_automasking_loss_sources": (C.c_int, [C.c_int, C.POINTER(LossSource), P, C.c_longlong, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, P, P]),
+    "md2_model_forward_loss_stereo": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P, P]),
+    "md2_model_train_step_graph_stereo": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P, C.c_float, C.c_int, P, P]),
     "md2_model_set_profiling": (C.c_int, [P, C.c_int]),
     "md2_model_profile_read": (C.c_int, [P, C.POINTER(C.c_double), C.c_int]),
     "md2_model_profile_records": (C.c_int, [P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_int), C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
 }
+
+
+# the sources (stereo) entry points, added without an ABI bump
+_SOURCES_SYMS = ("md2_loss_sources_workspace_size", "md2_loss_fwd_bwd_sources", "md2_automasking_loss_sources",
+                 "md2_model_forward_loss_stereo", "md2_model_train_step_graph_stereo")
 
 
 def lib():
@@ -297,6 +318,8 @@ def lib():
     import torch  # noqa: F401
     l = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in _SIGS.items():
+        if name in _SOURCES_SYMS and os.environ.get("MD2HIP_LIB") is not None and not hasattr(l, name):
+            continue     # an older library given for an A/B: it has no sources entry points to call
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

@@ -250,12 +250,18 @@ class KittyDataset(_Dataset):
     ``resize="host"`` resizes on the loader's host threads (``md2_load_kitti_u8``, imresize);
     ``resize="device"`` decodes the frames at their own sizes (``batch_native``) and leaves the resize
     to ``md2_resize_frames`` on the GPU, which ``DataLoader`` drives; ``filter`` is then
-    ``"imresize"`` (the host path's bytes) or ``"antialias"``."""
+    ``"imresize"`` (the host path's bytes) or ``"antialias"``.
+
+    ``stereo=True`` (``resize="device"`` only): a sample carries a fourth frame, the other camera of
+    the rig (``image_0`` <-> ``image_1``, ``image_2`` <-> ``image_3``) at the target's frame index,
+    loaded, resized and mirrored exactly as the sample's own frames.  ``side`` is "l" for
+    ``image_0`` / ``image_2`` and "r" otherwise (``md2hip.stereo_transforms``)."""
 
     CAMERAS = {"image_0": 1, "image_1": 1, "image_2": 3, "image_3": 3}
+    PARTNER = {"image_0": "image_1", "image_1": "image_0", "image_2": "image_3", "image_3": "image_2"}
 
     def __init__(self, image_dir: str, sequence: str, *, target_size, augmentations=None,
-                 camera: str = "image_0", resize: str = "host", filter: str = "imresize"):
+                 camera: str = "image_0", resize: str = "host", filter: str = "imresize", stereo: bool = False):
         from ._lib import RESIZE_FILTERS
         if camera not in self.CAMERAS:
             raise ValueError(f"camera must be one of {sorted(self.CAMERAS)}, got {camera!r}")
@@ -268,10 +274,18 @@ class KittyDataset(_Dataset):
         if resize == "host" and self.CAMERAS[camera] != 1:
             raise ValueError(f'camera="{camera}" is a colour camera: it needs resize="device" '
                              "(the host path reads 8-bit grayscale)")
+        if stereo and resize != "device":
+            raise ValueError('stereo=True needs resize="device": the partner frame rides the device route '
+                             "(md2_load_frames_native_u8 + md2_resize_frames take any number of frames)")
         seq_dir = os.path.join(image_dir, "sequences", sequence)
         with open(os.path.join(seq_dir, "calib.txt")) as f:
             K0 = _parse_calib_P0(f.readline())
         self.frames_dir = os.path.join(seq_dir, camera)
+        self.stereo = bool(stereo)
+        self.side = "l" if camera in ("image_0", "image_2") else "r"
+        self.partner_dir = os.path.join(seq_dir, self.PARTNER[camera])
+        if self.stereo and not os.path.isdir(self.partner_dir):
+            raise ValueError(f"stereo=True: the partner camera's frames are missing ({self.partner_dir})")
         files = sorted(os.listdir(self.frames_dir))
         n_frames = len(files)
         first = os.path.join(self.frames_dir, files[0])
@@ -282,6 +296,8 @@ class KittyDataset(_Dataset):
         self.invK = np.linalg.inv(self.K)
         self.resolution = (width, height)
         self.frame_ids = (1, 2, 3)
+        self.target_id = 2
+        self.frames_per_sample = len(self.frame_ids) + (1 if self.stereo else 0)
         self.total_length = n_frames // len(self.frame_ids)
         self.augmentations = augmentations
         self.channels = self.CAMERAS[camera]
@@ -295,9 +311,18 @@ class KittyDataset(_Dataset):
     def __len__(self):
         return self.total_length
 
+    def partner_path(self, i):
+        """The other camera's frame at sample i's target index."""
+        return os.path.join(self.partner_dir, "%06d.png" % (i * len(self.frame_ids) + self.target_id - 1))
+
     def _paths(self, idx):
-        return [os.path.join(self.frames_dir, "%06d.png" % (i * len(self.frame_ids) + x - 1)).encode()
-                for i in idx for x in self.frame_ids]
+        out = []
+        for i in idx:
+            out += [os.path.join(self.frames_dir, "%06d.png" % (i * len(self.frame_ids) + x - 1)).encode()
+                    for x in self.frame_ids]
+            if self.stereo:
+                out.append(self.partner_path(i).encode())
+        return out
 
     def _native_load(self, idx, flips, out, threads):
         from ._lib import check, lib
@@ -312,9 +337,10 @@ class KittyDataset(_Dataset):
     def batch_native(self, idx, seed: int = 0, threads: int = 8, out=None):
         """Samples ``idx`` decoded at their own sizes (md2_load_frames_native_u8 on ``threads`` host
         threads), for ``md2hip.resize_frames``: ``(buf, offsets, sizes, flips)`` -- ``buf`` uint8
-        [len(idx) * 3 * slot_bytes] (``out``: a caller buffer, e.g. pinned) holding frame k of the
-        flat list at ``offsets[k] = k * slot_bytes`` as rows of interleaved pixels, ``sizes[k] =
-        (h, w)``, ``flips[k]`` the FlipX coin of its sample."""
+        [len(idx) * frames_per_sample * slot_bytes] (``out``: a caller buffer, e.g. pinned) holding
+        frame k of the flat list at ``offsets[k] = k * slot_bytes`` as rows of interleaved pixels,
+        ``sizes[k] = (h, w)``, ``flips[k]`` the FlipX coin of its sample.  A sample is its three frames
+        and, with ``stereo``, the partner frame as the fourth."""
         from ._lib import check, lib
         if self.resize != "device":
             raise TypeError('batch_native is the resize="device" route')
@@ -331,16 +357,20 @@ class KittyDataset(_Dataset):
                                               h.ctypes.data_as(C.POINTER(C.c_int)), threads),
               "md2_load_frames_native_u8")
         return (out, np.arange(n, dtype=np.int64) * self.slot_bytes, np.stack([h, w], 1).astype(np.int64),
-                np.repeat(coins, len(self.frame_ids)))
+                np.repeat(coins, self.frames_per_sample))
 
     def getobs_u8(self, i: int, seed: int = 0) -> np.ndarray:
         """Sample ``i`` (0-based): frames 3i, 3i+1, 3i+2 (kitty.jl:47-61), each ``imresize``d to
-        the target size and kept N0f8 -> uint8 [3][C][H][W] (the host restatement; imresize only)."""
+        the target size and kept N0f8 -> uint8 [3][C][H][W] (the host restatement; imresize only).
+        With ``stereo`` [4][C][H][W]: the partner frame last, resized and mirrored like the others."""
         width, height = self.resolution
         sid = i * len(self.frame_ids)
         frames = []
-        for x in self.frame_ids:
-            img = _load_png_raw(os.path.join(self.frames_dir, "%06d.png" % (sid + x - 1)))
+        files = [os.path.join(self.frames_dir, "%06d.png" % (sid + x - 1)) for x in self.frame_ids]
+        if self.stereo:
+            files.append(self.partner_path(i))
+        for path in files:
+            img = _load_png_raw(path)
             if img.dtype != np.uint8 or img.shape[0] != self.channels:
                 raise TypeError(f"KITTI {self.camera} frames are 8-bit " + ("grayscale" if self.channels == 1 else "RGB"))
             if self.filter != "imresize":
@@ -364,6 +394,8 @@ class DChain:
             raise ValueError("DChain members mix host and device resize: a batch takes one route -- give every "
                              'KittyDataset the same resize=, or chain the resize="device" ones on their own')
         self.resize = routes.pop() if routes else "host"
+        if any(getattr(d, "stereo", False) for d in self.datasets):
+            raise ValueError("DChain does not chain stereo=True datasets (a member's side is its own)")
         if self.resize == "device":
             if len({(d.channels, d.filter, tuple(d.resolution)) for d in self.datasets}) > 1:
                 raise ValueError('DChain members with resize="device" must share channels, filter and target size')
@@ -454,11 +486,22 @@ class DataLoader:
     A dataset with ``resize="device"`` (``KittyDataset``; GPU loaders only) is decoded at its frames'
     own sizes into pinned slots (``batch_native``), copied in one piece and resized on the side stream
     by ``md2_resize_frames``, FlipX and the N0f8 -> Float32 conversion included; with
-    ``filter="imresize"`` the batch equals the ``resize="host"`` loader's bit for bit."""
+    ``filter="imresize"`` the batch equals the ``resize="host"`` loader's bit for bit.
+    ``stereo=True`` (a ``KittyDataset(..., resize="device", stereo=True)``): the loader yields
+    ``(x, x_stereo, stereo_Rt)`` -- or ``(x, x_net, x_stereo, stereo_Rt)`` with ``color_jitter`` --
+    where x_stereo [N][C][H][W] is the partner camera's frame at the target's index, resized and
+    mirrored with its sample, and stereo_Rt [N][12] is ``md2hip.stereo_transforms`` of the dataset's
+    side and the samples' FlipX coins.  Colour jitter does not touch x_stereo: only the loss reads it."""
 
     def __init__(self, dataset, batch_size: int, *, shuffle: bool = True, seed: int = 0,
                  workers: int = 8, device=None, rank: int = 0, world: int = 1, prefetch: int = 2,
-                 bytes_h2d: bool = True, native: bool = True, color_jitter=None):
+                 bytes_h2d: bool = True, native: bool = True, color_jitter=None, stereo: bool = False):
+        if stereo and getattr(dataset, "resize", "host") != "device":
+            raise ValueError('stereo=True needs a dataset with resize="device" (the partner frame rides the '
+                             "device route)")
+        if bool(stereo) != bool(getattr(dataset, "stereo", False)):
+            raise ValueError("DataLoader(stereo=...) and the dataset's stereo= must agree")
+        self.stereo = bool(stereo)
         self.ds, self.batch_size, self.shuffle, self.seed = dataset, batch_size, shuffle, seed
         self.workers, self.rank, self.world, self.prefetch = workers, rank, world, prefetch
         self.bytes_h2d, self.native = bytes_h2d, native
@@ -506,14 +549,15 @@ class DataLoader:
         else:
             get = lambda i: self.ds.getobs(i, seed=self.seed + epoch)
         w_, h_ = self.ds.resolution
-        shape = (self.batch_size, 3, self.ds.channels, h_, w_)
+        nf = 4 if self.stereo else 3
+        shape = (self.batch_size, nf, self.ds.channels, h_, w_)
         jobs = max(1, min(self.prefetch, len(batches)))
         per_call = max(1, self.workers // jobs)
 
         def native_batch(idx):
             # the library's PNG decoder on per_call host threads, straight into (pinned) memory
             if dev_resize:   # frames at their own sizes, one slot each; the GPU resizes
-                buf = torch.empty(len(idx) * 3 * self.ds.slot_bytes, dtype=torch.uint8, pin_memory=True)
+                buf = torch.empty(len(idx) * nf * self.ds.slot_bytes, dtype=torch.uint8, pin_memory=True)
                 return self.ds.batch_native(idx, seed=self.seed + epoch, threads=per_call, out=buf)
             buf = torch.empty(shape, dtype=torch.uint8, pin_memory=on_gpu)
             self.ds.batch_u8(idx, seed=self.seed + epoch, threads=per_call, out=buf)
@@ -561,8 +605,17 @@ class DataLoader:
                                                                     C.c_void_p(stream.cuda_stream)),
                                           "md2_unorm8_to_float")
                                     x = xf
+                                extra = ()
+                                if self.stereo:     # the fourth frame of every sample and its transform
+                                    from .loss import stereo_transforms
+                                    Rt = stereo_transforms([self.ds.side] * len(cur), flips[::nf])
+                                    extra = (x[:, 3].contiguous(),
+                                             torch.from_numpy(Rt).pin_memory().to(dev, non_blocking=True))
+                                    x = x[:, :3].contiguous()
                                 if jitter is not None:   # the networks' input; x itself stays as loaded
-                                    x = (x, jitter(x, jitter.draw(cur, self.seed + epoch)))
+                                    x = (x, jitter(x, jitter.draw(cur, self.seed + epoch))) + extra
+                                elif extra:
+                                    x = (x,) + extra
                                 ev = torch.cuda.Event()
                                 ev.record(stream)
                             q.put((x, ev, host))

@@ -43,7 +43,8 @@ def depth10k_intrinsics(width=416, height=128):
 
 def _check_ids(cache: TrainCache):
     if len(cache.source_ids) != 2:
-        raise ValueError("the HIP loss supports exactly two source frames (TrainCache.source_ids)")
+        raise ValueError("the HIP loss supports exactly two source frames (TrainCache.source_ids); "
+                         "a stereo source is not a frame id -- pass it as x_stereo / stereo_Rt")
 
 
 def make_loss_cfg(N, C_, W, H, disp_shapes, cache: TrainCache, params: Params, *,
@@ -82,9 +83,79 @@ def pack_poses(poses):
     return torch.cat([torch.cat([r, t], 1) for r, t in poses], 0).contiguous()
 
 
+def stereo_transforms(sides, flips=None, baseline=0.1):
+    """Fixed transforms of the stereo partner, one per sample: [N, 12] float32 (NumPy), rows
+    (R row-major, t) with R = I and t = (side_sign * flip_sign * baseline, 0, 0).
+
+    sides: "l" / "r" per sample, the camera of the TARGET (side_sign -1 for "l", +1 for "r");
+    flips: per sample, true where the sample is mirrored (flip_sign -1), None = none.  This is
+    Monodepth2's ``stereo_T[0, 3] = side_sign * baseline_sign * 0.1``.  The baseline is 0.1 and not
+    KITTI's 0.54 m on purpose: depths then come out in units of 5.4 m, the ``scale=5.4`` that
+    ``depth_errors(median_scaling=False, scale=5.4)`` multiplies back in."""
+    sides = list(sides)
+    flips = [False] * len(sides) if flips is None else [bool(f) for f in flips]
+    if len(flips) != len(sides):
+        raise ValueError("sides and flips differ in length")
+    Rt = np.zeros((len(sides), 12), dtype=np.float32)
+    Rt[:, 0] = Rt[:, 4] = Rt[:, 8] = 1.0
+    for i, (s, f) in enumerate(zip(sides, flips)):
+        if s not in ("l", "r"):
+            raise ValueError(f"side must be 'l' or 'r', got {s!r}")
+        Rt[i, 9] = np.float32((-1.0 if s == "l" else 1.0) * (-1.0 if f else 1.0) * baseline)
+    return Rt
+
+
+def check_stereo(x, x_stereo, stereo_Rt):
+    """Shape / dtype / device checks of a stereo source against x [N,3,C,H,W] (the kernels read raw
+    pointers): x_stereo [N,C,H,W] and stereo_Rt [N,12], float32, contiguous, on x's device."""
+    import torch
+    N, L, C_, H, W = x.shape
+    if stereo_Rt is None:
+        raise ValueError("x_stereo needs stereo_Rt ([N, 12]; md2hip.stereo_transforms)")
+    for name, t, shape in (("x_stereo", x_stereo, (N, C_, H, W)), ("stereo_Rt", stereo_Rt, (N, 12))):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if t.device != x.device:
+            raise ValueError(f"{name} is on {t.device}, x on {x.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if L != 3:
+        raise ValueError("x must hold 3 frames")
+
+
+def stereo_sources(x, x_stereo, stereo_Rt, cache: TrainCache, temporal=True):
+    """The ``md2_loss_source`` array of MS (temporal: the two temporal sources of ``cache``, learned,
+    then the stereo frame, fixed -- Monodepth2's [0, -1, 1, "s"]) or of S (the stereo frame alone).
+    Returns (array, nsrc, n_learned)."""
+    N, L, C_, H, W = x.shape
+    fs = C_ * H * W
+    ids = list(cache.source_ids) if temporal else []
+    if temporal:
+        _check_ids(cache)
+    arr = (_lib.LossSource * _lib.MAX_SOURCES)()
+    for s, sid in enumerate(ids):
+        arr[s].frames = x.data_ptr() + 4 * (sid - 1) * fs
+        arr[s].sample_stride = L * fs
+        arr[s].pose_block = s
+        arr[s].invert = int(sid < cache.target_id)
+        arr[s].Rt = None
+    k = len(ids)
+    arr[k].frames = x_stereo.data_ptr()
+    arr[k].sample_stride = fs
+    arr[k].pose_block = -1
+    arr[k].invert = 0
+    arr[k].Rt = stereo_Rt.data_ptr()
+    return arr, k + 1, k
+
+
 def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Params, *,
               grads=True, smooth_weights=None, divisor=None, smooth_normalize=True,
-              dloss=1.0, sigmoid_grad=False, visualize=False, keep_workspace=False):
+              dloss=1.0, sigmoid_grad=False, visualize=False, keep_workspace=False,
+              x_stereo=None, stereo_Rt=None, temporal=True):
     """The body of ``train_loss`` after the model call (src/training.jl:25-77) and its pullback.
 
     disparities: list of [N,1,h,w] float32 CUDA tensors (one per scale); poses: list of
@@ -92,8 +163,23 @@ def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Param
     Returns a dict: loss [1], terms [nscales,2], d_disp (list), d_pose [2N,6] and, with
     ``visualize``, vis_loss / vis_sel [nscales,N,H,W] (training.jl:71-74 vis_loss) and
     vis_warped [2,N,C,H,W] (both sources warped by the last scale, training.jl:71-73).
-    ``keep_workspace`` (diagnostics): also return the raw workspace as "workspace"."""
+    ``keep_workspace`` (diagnostics): also return the raw workspace as "workspace".
+
+    Stereo supervision: with ``x_stereo`` [N,C,H,W] (the other camera's frame at the target's time)
+    and ``stereo_Rt`` [N,12] (``stereo_transforms``) the loss runs over the sources
+    (source_ids[0], source_ids[1], stereo) -- "MS", ``temporal=True`` -- or over the stereo frame
+    alone -- "S", ``temporal=False``, where ``poses`` is not read and d_pose is None.  The stereo
+    transform is data: it gets no gradient.  vis_sel then holds 0..S-1 (the stereo frame last) or
+    -1, vis_warped is [S,N,C,H,W] and vis_cell [nscales,S,N,H,W]; an ``auto_loss`` of None is
+    computed over the same sources."""
     import torch
+    if x_stereo is not None:
+        return _loss_tail_sources(disparities, poses, x, auto_loss, cache, params, x_stereo, stereo_Rt,
+                                  temporal, grads=grads, smooth_weights=smooth_weights, divisor=divisor,
+                                  smooth_normalize=smooth_normalize, dloss=dloss, sigmoid_grad=sigmoid_grad,
+                                  visualize=visualize, keep_workspace=keep_workspace)
+    if stereo_Rt is not None or not temporal:
+        raise ValueError("stereo_Rt / temporal=False need x_stereo")
     N, L, C_, H, W = x.shape
     dev = x.device
     for d in disparities:
@@ -139,3 +225,82 @@ def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Param
                                  C.c_float(dloss), C.byref(out), ptr(ws), stream_of(dev)),
           "md2_loss_fwd_bwd")
     return res
+
+
+def _sources_cfg(N, C_, W, H, shapes, cache, params, **kw):
+    """md2_loss_cfg of the sources form: the frame ids and strides of cfg are not read there."""
+    two = TrainCache(K=cache.K, invK=cache.invK, target_id=cache.target_id, source_ids=(1, 3),
+                     scales=cache.scales)
+    return make_loss_cfg(N, C_, W, H, shapes, two, params, **kw)
+
+
+def run_loss_sources(disparities, pose, x, target, target_stride, sources, nsrc, n_learned, auto_loss,
+                     cache, params, *, grads=True, smooth_weights=None, divisor=None,
+                     smooth_normalize=True, dloss=1.0, sigmoid_grad=False, visualize=False,
+                     keep_workspace=False):
+    """md2_loss_fwd_bwd_sources on an ``md2_loss_source`` array (``stereo_sources``; the tests build
+    their own).  x only gives the shape [N,L,C,H,W] and the device; target is a device address."""
+    import torch
+    N, L, C_, H, W = x.shape
+    dev = x.device
+    for d in disparities:
+        assert d.dtype == torch.float32 and d.is_contiguous() and d.device == dev
+    shapes = [(d.shape[-2], d.shape[-1]) for d in disparities]
+    cfg = _sources_cfg(N, C_, W, H, shapes, cache, params, smooth_weights=smooth_weights,
+                       divisor=divisor, smooth_normalize=smooth_normalize, L=L, sigmoid_grad=sigmoid_grad)
+    ws_bytes = lib().md2_loss_sources_workspace_size(C.byref(cfg), nsrc)
+    ws = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev)
+    ns = len(disparities)
+    res = {"loss": torch.empty(1, dtype=torch.float32, device=dev),
+           "terms": torch.empty(ns, 2, dtype=torch.float32, device=dev),
+           "d_disp": [torch.empty_like(d) for d in disparities] if grads else [None] * ns,
+           "d_pose": (torch.empty(n_learned * N, 6, dtype=torch.float32, device=dev)
+                      if grads and n_learned > 0 else None)}
+    if keep_workspace:
+        res["workspace"] = ws
+    if visualize:
+        res["vis_loss"] = torch.empty(ns, N, H, W, dtype=torch.float32, device=dev)
+        res["vis_sel"] = torch.empty(ns, N, H, W, dtype=torch.int8, device=dev)
+        res["vis_warped"] = torch.empty(nsrc, N, C_, H, W, dtype=torch.float32, device=dev)
+        res["vis_cell"] = torch.empty(ns, nsrc, N, H, W, dtype=torch.int32, device=dev)
+    am = None
+    if params.automasking:
+        if auto_loss is None:
+            am = torch.empty(N, 1, H, W, dtype=torch.float32, device=dev)
+            check(lib().md2_automasking_loss_sources(nsrc, sources, C.c_void_p(target), target_stride, N, C_,
+                                                     H, W, ptr(am), stream_of(dev)),
+                  "md2_automasking_loss_sources")
+        else:
+            am = auto_loss.contiguous()
+            if tuple(am.shape) != (N, 1, H, W) or am.dtype != torch.float32 or am.device != dev:
+                raise ValueError(f"auto_loss must be float32 [N,1,H,W] = {(N, 1, H, W)} on {dev}")
+    out = _lib.LossOut()
+    out.loss = res["loss"].data_ptr()
+    out.terms = res["terms"].data_ptr()
+    for i, d in enumerate(res["d_disp"]):
+        out.d_disp[i] = None if d is None else d.data_ptr()
+    out.d_pose = None if res["d_pose"] is None else res["d_pose"].data_ptr()
+    out.vis_loss = res["vis_loss"].data_ptr() if visualize else None
+    out.vis_sel = res["vis_sel"].data_ptr() if visualize else None
+    out.vis_warped = res["vis_warped"].data_ptr() if visualize else None
+    out.vis_cell = res["vis_cell"].data_ptr() if visualize else None
+    disp_arr = ptr_array(disparities)
+    check(lib().md2_loss_fwd_bwd_sources(C.byref(cfg), nsrc, sources, C.c_void_p(target), target_stride,
+                                         C.cast(disp_arr, _lib.FP), ptr(pose), ptr(am), C.c_float(dloss),
+                                         C.byref(out), ptr(ws), stream_of(dev)),
+          "md2_loss_fwd_bwd_sources")
+    return res
+
+
+def _loss_tail_sources(disparities, poses, x, auto_loss, cache, params, x_stereo, stereo_Rt, temporal, **kw):
+    import torch
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    check_stereo(x, x_stereo, stereo_Rt)
+    N, L, C_, H, W = x.shape
+    sources, nsrc, n_learned = stereo_sources(x, x_stereo, stereo_Rt, cache, temporal)
+    pose = pack_poses(poses).to(x.device, torch.float32) if temporal else None
+    if pose is not None and tuple(pose.shape) != (2 * N, 6):
+        raise ValueError(f"poses must pack to [2N, 6] = {(2 * N, 6)}, got {tuple(pose.shape)}")
+    target = x.data_ptr() + 4 * (cache.target_id - 1) * C_ * H * W
+    return run_loss_sources(disparities, pose, x, target, L * C_ * H * W, sources, nsrc, n_learned,
+                            auto_loss, cache, params, **kw)

@@ -276,15 +276,36 @@ class _Executor:
                 or not x_net.is_contiguous()):
             raise ValueError("x_net must be a contiguous float32 tensor shaped and placed like x")
 
-    def forward_loss(self, x, auto_loss=None, loss=None, terms=None, x_net=None):
+    def _check_stereo(self, x, x_stereo, stereo_Rt, temporal):
+        from .loss import check_stereo
+        if x_stereo is None:
+            if stereo_Rt is not None or not temporal:
+                raise ValueError("stereo_Rt / temporal=False need x_stereo")
+            return False
+        check_stereo(x, x_stereo, stereo_Rt)
+        return True
+
+    def forward_loss(self, x, auto_loss=None, loss=None, terms=None, x_net=None, x_stereo=None,
+                     stereo_Rt=None, temporal=True):
         """``x_net`` (like x, e.g. ``color_jitter(x, ...)``): the frames the networks see; the automask
-        and the loss tail read x (md2_model_forward_loss_aug).  None: the plain call."""
+        and the loss tail read x (md2_model_forward_loss_aug).  None: the plain call.
+        ``x_stereo`` [N,C,H,W] with ``stereo_Rt`` [N,12] (``stereo_transforms``): stereo supervision
+        (md2_model_forward_loss_stereo) -- ``temporal=True`` "MS", the loss over both temporal sources
+        and the stereo frame; ``temporal=False`` "S", the stereo frame alone (the pose network's
+        gradient is then zero).  Only the loss and the automask read the stereo frame."""
         import torch
         self.model._require_train("train_loss / forward_loss")
         loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=x.device)
         self.sync()
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
-        if x_net is None:
+        if self._check_stereo(x, x_stereo, stereo_Rt, temporal):
+            if x_net is not None:
+                self._check_net(x, x_net)
+            check(lib().md2_model_forward_loss_stereo(self.handle, ptr(x), ptr(x_net), ptr(x_stereo), ptr(stereo_Rt),
+                                                      int(bool(temporal)), ptr(am), ptr(loss), ptr(terms),
+                                                      stream_of(x.device)), "md2_model_forward_loss_stereo")
+            self._stereo_keep = (x_stereo, stereo_Rt)     # read asynchronously
+        elif x_net is None:
             check(lib().md2_model_forward_loss(self.handle, ptr(x), ptr(am), ptr(loss), ptr(terms),
                                                stream_of(x.device)), "md2_model_forward_loss")
         else:
@@ -325,8 +346,11 @@ class _Executor:
         self._cot_keep = (keep, dp)           # the copies are async: keep the sources alive
         self.cotangents = True
 
-    def train_step_graph(self, x, opt: "ADAM", auto_loss=None, loss=None, x_net=None):
-        """One full step (forward, loss, backward, Flux ADAM with opt's state) replayed as a
+    def train_step_graph(self, x, opt: "ADAM", auto_loss=None, loss=None, x_net=None, x_stereo=None,
+                         stereo_Rt=None, temporal=True):
+        """``x_stereo`` / ``stereo_Rt`` / ``temporal`` as for ``forward_loss``
+        (md2_model_train_step_graph_stereo; captured again when the presence of the stereo source or
+        ``temporal`` changes).  One full step (forward, loss, backward, Flux ADAM with opt's state) replayed as a
         captured hipGraph (md2_model_train_step_graph): the same kernels in the same order as
         forward_loss + backward + ADAM.update, without per-launch host work.  Returns the loss.
         ``x_net`` as for ``forward_loss`` (md2_model_train_step_graph_aug; the step is captured again
@@ -341,9 +365,17 @@ class _Executor:
             opt.m = torch.zeros_like(self.model.flat)
             opt.v = torch.zeros_like(self.model.flat)
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
+        stereo = self._check_stereo(x, x_stereo, stereo_Rt, temporal)
         opt._apply_guard(self)
         opt.t += 1
-        if x_net is None:
+        if stereo:
+            if x_net is not None:
+                self._check_net(x, x_net)
+            check(lib().md2_model_train_step_graph_stereo(self.handle, ptr(x), ptr(x_net), ptr(x_stereo),
+                                                          ptr(stereo_Rt), int(bool(temporal)), ptr(am), ptr(opt.m),
+                                                          ptr(opt.v), opt.eta, opt.t, ptr(loss), stream_of(x.device)),
+                  "md2_model_train_step_graph_stereo")
+        elif x_net is None:
             check(lib().md2_model_train_step_graph(self.handle, ptr(x), ptr(am), ptr(opt.m), ptr(opt.v), opt.eta,
                                                    opt.t, ptr(loss), stream_of(x.device)),
                   "md2_model_train_step_graph")
@@ -582,18 +614,25 @@ def disparity_bins(batch: int, num_bins: int, u=None, device="cuda", near=1.0, f
 
 
 def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
-               do_visualization: bool = False, num_bins: int = 32, bins=None, x_net=None):
+               do_visualization: bool = False, num_bins: int = 32, bins=None, x_net=None, x_stereo=None,
+               stereo_Rt=None, temporal=True):
     """``train_loss(model, x, auto_loss, cache, params, do_visualization)`` (src/training.jl:21).
     Runs the forward and the fused loss-tail pullback; call ``gradient(model)`` for the rest of
     the backward.  Returns (loss, vis_disparity, vis_warped, vis_loss).  MPI mode (the model's
     DepthDecoder has embedding_levels > 0; batch 1): ``num_bins`` planes, ``bins`` [1, num_bins]
     (default: a fresh draw of md2hip.disparity_bins).  ``x_net`` (like x; not in MPI mode): the
-    colour-augmented frames the networks see, while the loss, SSIM and the automask stay on x."""
+    colour-augmented frames the networks see, while the loss, SSIM and the automask stay on x.
+    ``x_stereo`` [N,C,H,W], ``stereo_Rt`` [N,12] (``md2hip.stereo_transforms``), ``temporal``: stereo
+    supervision (not in MPI mode) -- "MS" (``temporal=True``: sources (source_ids[0], source_ids[1],
+    stereo), Monodepth2's [0, -1, 1, "s"]) or "S" (``temporal=False``: the stereo frame alone; the pose
+    network still runs and gets a zero gradient).  The networks never see the stereo frame; with
+    ``auto_loss=None`` the automask is taken over the same sources as the loss.  vis_warped then has
+    one entry per source."""
     model._require_train("train_loss")
     ex = model.executor(tuple(x.shape), cache, params, num_bins)
     if ex.emb:
         ex.set_bins(disparity_bins(x.shape[0], num_bins, device=x.device) if bins is None else bins)
-    loss = ex.forward_loss(x, auto_loss, x_net=x_net)
+    loss = ex.forward_loss(x, auto_loss, x_net=x_net, x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal)
     if not do_visualization:
         return loss, None, None, None
     # training.jl:34-37,71-74: the last disparity, both warped sources and the per-pixel warp
@@ -612,7 +651,8 @@ def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
     vis = loss_tail(disps, poses, xv, auto_loss, cache,
                     Params(target_size=params.target_size, batch_size=N * nb, min_depth=params.min_depth,
                            max_depth=params.max_depth, disparity_smoothness=params.disparity_smoothness,
-                           automasking=params.automasking), grads=False, visualize=True)
+                           automasking=params.automasking), grads=False, visualize=True,
+                    x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal)
     return (loss, disps[-1].cpu(), [w.cpu() for w in vis["vis_warped"].unbind(0)],
             vis["vis_loss"][-1].unsqueeze(1).cpu())
 
@@ -800,11 +840,13 @@ class ADAM:
         ex.version = model.version
 
 
-def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, opt: ADAM, x_net=None):
-    """One ``gradient(θ) do train_loss(...)[1] end`` + ``update!`` on one GPU (``x_net``: see
-    ``train_loss``)."""
+def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, opt: ADAM, x_net=None,
+               x_stereo=None, stereo_Rt=None, temporal=True):
+    """One ``gradient(θ) do train_loss(...)[1] end`` + ``update!`` on one GPU (``x_net``, ``x_stereo``,
+    ``stereo_Rt``, ``temporal``: see ``train_loss``)."""
     model._require_train("train_step")
-    loss, *_ = train_loss(model, x, auto_loss, cache, params, x_net=x_net)
+    loss, *_ = train_loss(model, x, auto_loss, cache, params, x_net=x_net, x_stereo=x_stereo,
+                          stereo_Rt=stereo_Rt, temporal=temporal)
     gradient(model)
     opt.update(model)
     return loss

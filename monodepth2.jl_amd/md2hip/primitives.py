@@ -51,12 +51,33 @@ def static_scores(x, target_id: int = 2, source_ids: Sequence[int] = (1, 3)):
     return out
 
 
-def automasking_loss(x, target_id: int = 2, source_ids: Sequence[int] = (1, 3)):
+def automasking_loss(x, target_id: int = 2, source_ids: Sequence[int] = (1, 3), *, x_stereo=None):
     """``automasking_loss(ssim, x, target; source_ids)`` (src/training.jl:9-11): x [N, 3, C, H, W]
-    -> [N, 1, H, W] identity-reprojection loss (min over the raw sources).  Data only."""
+    -> [N, 1, H, W] identity-reprojection loss (min over the raw sources).  Data only.
+    With ``x_stereo`` [N, C, H, W] the stereo frame is one more raw source, after ``source_ids``
+    (which may then hold 0, 1 or 2 frame ids)."""
     import torch
     _f32(x)
     N, L, Cc, H, W = x.shape
+    if x_stereo is not None:
+        from . import _lib
+        if (not isinstance(x_stereo, torch.Tensor) or tuple(x_stereo.shape) != (N, Cc, H, W)
+                or x_stereo.dtype != torch.float32 or x_stereo.device != x.device
+                or not x_stereo.is_contiguous()):
+            raise ValueError(f"x_stereo must be a contiguous float32 [N,C,H,W] = {(N, Cc, H, W)} tensor on {x.device}")
+        if L != 3 or len(source_ids) > 2 or any(not 1 <= s <= 3 for s in source_ids):
+            raise ValueError("x must hold 3 frames and source_ids at most two of them")
+        fs = Cc * H * W
+        arr = (_lib.LossSource * _lib.MAX_SOURCES)()
+        for s, sid in enumerate(source_ids):
+            arr[s].frames, arr[s].sample_stride, arr[s].pose_block = x.data_ptr() + 4 * (sid - 1) * fs, L * fs, -1
+        k = len(source_ids)
+        arr[k].frames, arr[k].sample_stride, arr[k].pose_block = x_stereo.data_ptr(), fs, -1
+        out = torch.empty(N, 1, H, W, dtype=torch.float32, device=x.device)
+        check(lib().md2_automasking_loss_sources(k + 1, arr, C.c_void_p(x.data_ptr() + 4 * (target_id - 1) * fs),
+                                                 L * fs, N, Cc, H, W, ptr(out), stream_of(x.device)),
+              "md2_automasking_loss_sources")
+        return out
     if L != 3 or len(source_ids) != 2:
         raise ValueError("x must hold 3 frames and source_ids two of them")
     out = torch.empty(N, 1, H, W, dtype=torch.float32, device=x.device)
