@@ -318,6 +318,116 @@ int md2_maxpool3s2_bwd(const float* dy, const unsigned char* arg, int n, int c, 
                        float* dx, void* stream);
 int md2_upsample2_fwd(const float* x, int n, int c, int h, int w, float* y, void* stream);
 int md2_upsample2_bwd(const float* dy, int n, int c, int h, int w, float* dx, void* stream);
+/* md2_maxpool3s2_bwd with the addend of the stem backward: dx += skip[e - skip_lo] over the flat
+ * elements [skip_lo, skip_hi) of dx (whole planes: both multiples of h*w; even w).  skip == NULL:
+ * md2_maxpool3s2_bwd.  MD2_EINVAL before any HIP call: a null dy / arg / dx, a size < 1, a range
+ * that is not 0 <= skip_lo <= skip_hi <= n*c*h*w on plane boundaries, an odd w with a skip. */
+int md2_maxpool3s2_bwd_ex(const float* dy, const unsigned char* arg, int n, int c, int h, int w,
+                          float* dx, const float* skip, long long skip_lo, long long skip_hi,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * BatchNorm of the encoder (Flux BatchNorm in trainmode!: batch mean, biased variance, eps) with
+ * the operand forms the train step feeds it (csrc/nn.h BNApplyFused / BNBwd), on caller-owned
+ * device buffers [n][c][h][w].  These calls launch the executor's kernels; where the executor
+ * reads its MD2_FUSE_* switches, the route is an argument here.  Additive: MD2_ABI_VERSION is
+ * unchanged.
+ *   route     0: the executor's choice -- one kernel where a channel fits in a block (h*w % 4 == 0
+ *             and n*h*w <= 8192) and the statistics are the call's own, else two passes;
+ *             1: two passes (partials, then finalise + apply); 2: one kernel (MD2_EINVAL where
+ *             the channel does not fit, with caller partials, or with pool outputs).
+ *   forward   out = act(gamma*(y-mean)*invstd + beta [+ gamma2*(y2-mean2)*invstd2 + beta2] [+ res]).
+ *             The input is y, or slab [splits][c][n*h*w] (a conv's split-K partials) summed in
+ *             split order into y_out.  The statistics are the call's own, or caller partials part
+ *             [c][parts][2] (fp64 sum and sum of squares; a conv epilogue's per-tile form), with
+ *             collapse = 1 first reduced to one partial per channel.  The second branch (y2) always
+ *             takes its own statistics pass.  mean / invstd (and mean2 / invstd2) are written;
+ *             run_mean / run_var (both or neither) are updated with momentum and the unbiased
+ *             variance.  pool_y / pool_arg (both or neither; relu = 1, no y2 / res, even h and w)
+ *             select the stem tail: out and its 3x3/2/pad-1 max pool [n][c][h/2][w/2] in one pass.
+ *   backward  g = (dout [+ skip[e - skip_lo] over flat elements [skip_lo, skip_hi)]) gated by
+ *             mask > 0 (the BN+ReLU output) or by the ReLU of BN(y) re-derived with mbeta;
+ *             dbeta = sum g, dgamma = sum g*xhat, dy = gamma*invstd*(g - dbeta/L - xhat*dgamma/L);
+ *             dres = g (dres_accumulate: += g).  The input is dout, or slab summed in split order;
+ *             two passes write that sum to dout_w, one kernel leaves dout_w untouched.
+ * Tensors are 16-byte aligned when h*w % 4 == 0 (float4 units; scalar units otherwise).
+ * MD2_EINVAL, checked before any HIP call: a null descriptor / operand struct / required pointer;
+ * a size < 1 or n*c*h*w >= 2^31; route outside 0..2, collapse / relu / dres_accumulate outside
+ * 0..1; route = 2 where the channel does not fit; both or neither of y and slab (dout and slab);
+ * slab without splits >= 1 or without y_out (dout_w on two passes); slab with caller partials, a
+ * mask or a skip; collapse without caller partials; parts < 1; y2 without gamma2 / beta2 / mean2 /
+ * invstd2; one of run_mean / run_var alone; mask together with mbeta; a skip with h*w % 4 != 0,
+ * outside 0 <= skip_lo <= skip_hi <= n*c*h*w, or with skip_lo / skip_hi not a multiple of 4 (the
+ * kernels read it in float4 units); pool outputs with odd h or w, y2, res, relu = 0 or one of the
+ * two alone; a misaligned tensor; a workspace smaller than md2_bn_ex_workspace_size or not
+ * 16-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct md2_bn_desc {
+  int n, c, h, w;
+  float eps, momentum;
+  int route;
+  int collapse;
+} md2_bn_desc;
+
+typedef struct md2_bn_info { /* out: what the call launched */
+  int family;    /* 1 two passes, 2 one kernel, 3 stem tail with the max pool */
+  int parts;     /* statistics / gradient partials per channel (0: one kernel) */
+  int fin_parts; /* partials per channel the apply's finalise walks (1 after a collapse) */
+  int upt;       /* units per thread of the apply pass (0: one kernel) */
+  int vec;       /* 1: float4 units, 0: scalar units */
+} md2_bn_info;
+
+typedef struct md2_bn_fwd_operands {
+  const float* y;
+  const float* slab;
+  float* y_out;
+  const double* part;
+  const float* gamma;
+  const float* beta;
+  float* mean;
+  float* invstd;
+  float* run_mean;
+  float* run_var;
+  const float* y2;
+  const float* gamma2;
+  const float* beta2;
+  float* mean2;
+  float* invstd2;
+  const float* res;
+  float* out;
+  float* pool_y;
+  unsigned char* pool_arg;
+  int splits, parts;
+  int relu;
+} md2_bn_fwd_operands;
+
+typedef struct md2_bn_bwd_operands {
+  const float* dout;
+  const float* slab;
+  float* dout_w;
+  const float* mask;
+  const float* y;
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  const float* mbeta;
+  float* dgamma;
+  float* dbeta;
+  float* dy;
+  float* dres;
+  const float* skip;
+  long long skip_lo, skip_hi;
+  int splits, dres_accumulate;
+} md2_bn_bwd_operands;
+
+/* bytes of workspace either call needs for this descriptor (0: invalid descriptor) */
+size_t md2_bn_ex_workspace_size(const md2_bn_desc* d);
+/* 1 where a channel of [n][c][h][w] fits in a block of the one-kernel passes, else 0 */
+int md2_bn_channel_fits(int n, long long hw);
+int md2_bn_forward_ex(const md2_bn_desc* d, const md2_bn_fwd_operands* o, md2_bn_info* info,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int md2_bn_backward_ex(const md2_bn_desc* d, const md2_bn_bwd_operands* o, md2_bn_info* info,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * MPI mode (src/model.jl:1-55; forward only upstream).  md2_mpi_embed_features

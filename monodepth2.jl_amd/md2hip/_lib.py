@@ -69,6 +69,33 @@ class ConvDefer(C.Structure):
     _fields_ = [("slab", C.c_void_p), ("defer_reduce", C.c_int), ("splits", C.c_int), ("stats_parts", C.c_int)]
 
 
+class BNDesc(C.Structure):
+    """``md2_bn_desc``."""
+    _fields_ = [("n", C.c_int), ("c", C.c_int), ("h", C.c_int), ("w", C.c_int), ("eps", C.c_float),
+                ("momentum", C.c_float), ("route", C.c_int), ("collapse", C.c_int)]
+
+
+class BNInfo(C.Structure):
+    """``md2_bn_info``."""
+    _fields_ = [(n, C.c_int) for n in ("family", "parts", "fin_parts", "upt", "vec")]
+
+
+class BNFwdOperands(C.Structure):
+    """``md2_bn_fwd_operands``."""
+    _fields_ = [(n, C.c_void_p) for n in ("y", "slab", "y_out", "part", "gamma", "beta", "mean", "invstd",
+                                          "run_mean", "run_var", "y2", "gamma2", "beta2", "mean2", "invstd2",
+                                          "res", "out", "pool_y", "pool_arg")] + \
+               [("splits", C.c_int), ("parts", C.c_int), ("relu", C.c_int)]
+
+
+class BNBwdOperands(C.Structure):
+    """``md2_bn_bwd_operands``."""
+    _fields_ = [(n, C.c_void_p) for n in ("dout", "slab", "dout_w", "mask", "y", "mean", "invstd", "gamma",
+                                          "mbeta", "dgamma", "dbeta", "dy", "dres", "skip")] + \
+               [("skip_lo", C.c_longlong), ("skip_hi", C.c_longlong), ("splits", C.c_int),
+                ("dres_accumulate", C.c_int)]
+
+
 class ModelCfg(C.Structure):
     """``md2_model_cfg``."""
     _fields_ = [
@@ -197,6 +224,14 @@ _SIGS = {
                             C.c_int, C.c_float, P]),
     "md2_maxpool3s2_fwd": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P]),
     "md2_maxpool3s2_bwd": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
+    "md2_maxpool3s2_bwd_ex": (C.c_int, [P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_longlong,
+                                        C.c_longlong, P]),
+    "md2_bn_ex_workspace_size": (C.c_size_t, [C.POINTER(BNDesc)]),
+    "md2_bn_channel_fits": (C.c_int, [C.c_int, C.c_longlong]),
+    "md2_bn_forward_ex": (C.c_int, [C.POINTER(BNDesc), C.POINTER(BNFwdOperands), C.POINTER(BNInfo), P,
+                                    C.c_size_t, P]),
+    "md2_bn_backward_ex": (C.c_int, [C.POINTER(BNDesc), C.POINTER(BNBwdOperands), C.POINTER(BNInfo), P,
+                                     C.c_size_t, P]),
     "md2_upsample2_fwd": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "md2_upsample2_bwd": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "md2_arch_param_count": (C.c_int, [C.POINTER(ModelCfg), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -304,6 +339,8 @@ _SIGS = {
 # the sources (stereo) entry points, added without an ABI bump
 _SOURCES_SYMS = ("md2_loss_sources_workspace_size", "md2_loss_fwd_bwd_sources", "md2_automasking_loss_sources",
                  "md2_model_forward_loss_stereo", "md2_model_train_step_graph_stereo")
+_BN_EX_SYMS = ("md2_maxpool3s2_bwd_ex", "md2_bn_ex_workspace_size", "md2_bn_channel_fits", "md2_bn_forward_ex",
+               "md2_bn_backward_ex")
 
 
 def lib():
@@ -318,8 +355,8 @@ def lib():
     import torch  # noqa: F401
     l = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in _SIGS.items():
-        if name in _SOURCES_SYMS and os.environ.get("MD2HIP_LIB") is not None and not hasattr(l, name):
-            continue     # an older library given for an A/B: it has no sources entry points to call
+        if name in _SOURCES_SYMS + _BN_EX_SYMS and os.environ.get("MD2HIP_LIB") is not None and not hasattr(l, name):
+            continue     # an older library given for an A/B: it has no such entry points to call
         f = getattr(l, name)
         f.restype = res
         f.argtypes = args

@@ -142,6 +142,83 @@ def conv2d_wgrad_ex(d, o, x, dy, dw, db=None, db_part=None, ws=None):
     return _ex_result(None, ws, 0, 0)
 
 
+def bn_desc(shape, eps=1e-5, momentum=0.1, route=0, collapse=False) -> "_lib.BNDesc":
+    """``md2_bn_desc`` of an [n, c, h, w] BatchNorm; route 0 = the executor's choice, 1 = two
+    passes, 2 = one kernel."""
+    n, c, h, w = shape
+    return _lib.BNDesc(n=n, c=c, h=h, w=w, eps=eps, momentum=momentum, route=route, collapse=int(bool(collapse)))
+
+
+def bn_ex_workspace(d, dev):
+    import torch
+    nbytes = lib().md2_bn_ex_workspace_size(C.byref(d))
+    if nbytes == 0:
+        raise ValueError("md2_bn_ex_workspace_size: invalid BatchNorm description")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+
+
+def _bn_operands(S, tensors, ints):
+    o = S()
+    for k, t in tensors.items():
+        setattr(o, k, None if t is None else t.data_ptr())
+    for k, v in ints.items():
+        setattr(o, k, int(v))
+    o._keep = tuple(tensors.values())
+    return o
+
+
+def _bn_info(inf):
+    return {"family": {1: "two_pass", 2: "one_kernel", 3: "stem_pool"}.get(inf.family, inf.family),
+            "parts": inf.parts, "fin_parts": inf.fin_parts, "upt": inf.upt, "vec": bool(inf.vec)}
+
+
+def bn_forward_ex(d, out, gamma, beta, mean, invstd, y=None, slab=None, y_out=None, part=None, run_mean=None,
+                  run_var=None, y2=None, gamma2=None, beta2=None, mean2=None, invstd2=None, res=None, relu=False,
+                  pool_y=None, pool_arg=None, ws=None):
+    """``md2_bn_forward_ex`` on caller-owned buffers (tensors or views give the base pointers).
+    ``slab`` [splits, c, n*h*w] is summed into ``y_out``; ``part`` [c, parts, 2] float64 are
+    caller statistics partials.  Returns {family, parts, fin_parts, upt, vec}."""
+    dev = out.device
+    ws = bn_ex_workspace(d, dev) if ws is None else ws
+    o = _bn_operands(_lib.BNFwdOperands,
+                     dict(y=y, slab=slab, y_out=y_out, part=part, gamma=gamma, beta=beta, mean=mean, invstd=invstd,
+                          run_mean=run_mean, run_var=run_var, y2=y2, gamma2=gamma2, beta2=beta2, mean2=mean2,
+                          invstd2=invstd2, res=res, out=out, pool_y=pool_y, pool_arg=pool_arg),
+                     dict(splits=0 if slab is None else slab.shape[0], parts=0 if part is None else part.shape[1],
+                          relu=bool(relu)))
+    inf = _lib.BNInfo()
+    check(lib().md2_bn_forward_ex(C.byref(d), C.byref(o), C.byref(inf), ptr(ws), ws.numel() * ws.element_size(),
+                                  stream_of(dev)), "md2_bn_forward_ex")
+    return _bn_info(inf)
+
+
+def bn_backward_ex(d, y, mean, invstd, gamma, dgamma, dbeta, dy, dout=None, slab=None, dout_w=None, mask=None,
+                   mbeta=None, dres=None, dres_accumulate=False, skip=None, skip_lo=0, skip_hi=0, ws=None):
+    """``md2_bn_backward_ex``: ``dout`` or ``slab`` [splits, c, n*h*w] (two passes write the sum
+    to ``dout_w``), gated by ``mask`` > 0 or by the ReLU re-derived from ``y`` with ``mbeta``;
+    ``skip`` is added over the flat elements [skip_lo, skip_hi).  Returns the info record."""
+    dev = dy.device
+    ws = bn_ex_workspace(d, dev) if ws is None else ws
+    o = _bn_operands(_lib.BNBwdOperands,
+                     dict(dout=dout, slab=slab, dout_w=dout_w, mask=mask, y=y, mean=mean, invstd=invstd, gamma=gamma,
+                          mbeta=mbeta, dgamma=dgamma, dbeta=dbeta, dy=dy, dres=dres, skip=skip),
+                     dict(skip_lo=skip_lo, skip_hi=skip_hi, splits=0 if slab is None else slab.shape[0],
+                          dres_accumulate=bool(dres_accumulate)))
+    inf = _lib.BNInfo()
+    check(lib().md2_bn_backward_ex(C.byref(d), C.byref(o), C.byref(inf), ptr(ws), ws.numel() * ws.element_size(),
+                                   stream_of(dev)), "md2_bn_backward_ex")
+    return _bn_info(inf)
+
+
+def maxpool3s2_backward_ex(dy, arg, dx, skip=None, skip_lo=0, skip_hi=0):
+    """``md2_maxpool3s2_bwd_ex`` into the caller's ``dx`` [n, c, h, w]: the pool's pullback plus
+    ``skip`` over the flat elements [skip_lo, skip_hi) (whole planes)."""
+    n, c, h, w = dx.shape
+    check(lib().md2_maxpool3s2_bwd_ex(ptr(dy), ptr(arg), n, c, h, w, ptr(dx), ptr(skip), skip_lo, skip_hi,
+                                      stream_of(dy.device)), "md2_maxpool3s2_bwd_ex")
+    return dx
+
+
 def act_backward_bias(out, dout, act):
     """:func:`act_backward` over [n, c, h, w] fused with the per-channel partial sums of dpre:
     returns (dpre, part [c, parts])."""

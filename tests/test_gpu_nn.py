@@ -61,6 +61,35 @@ def test_maxpool3s2(shape):
     assert D.rel_err(dx.cpu().double(), ref) < 1e-7
 
 
+@pytest.mark.parametrize("shape", [(3, 4, 6, 8), (2, 3, 7, 8)])
+def test_maxpool3s2_backward_with_skip(shape):
+    """md2_maxpool3s2_bwd_ex (the stem backward's form: the pool's pullback plus the decoder skip
+    gradient over the middle image) is md2_maxpool3s2_bwd followed by one fp32 add over the range,
+    bit for bit; nothing outside dx is written; skip == NULL is the plain call."""
+    ops = _ops()
+    n, c, h, w = shape
+    g = torch.Generator().manual_seed(13)
+    x = torch.round(torch.randn(*shape, generator=g) * 2)           # ties as well
+    y, arg = ops.maxpool3s2(x.to(DEV))
+    dy = torch.randn(*y.shape, generator=g).to(DEV)
+    plain = ops.maxpool3s2_backward(dy, arg, shape).cpu()
+    chw = c * h * w
+    lo, hi = chw, 2 * chw                                            # image 1: the middle image, or the last of two
+    skip = torch.randn(hi - lo, generator=g)
+    want = plain.clone().view(-1)
+    want[lo:hi] += skip
+    numel, guard, sent = n * chw, 64, 7168.5
+    for sk in (skip, None):
+        buf = torch.full((numel + 2 * guard,), sent, device=DEV)
+        dx = buf[guard:guard + numel].view(*shape)
+        ops.maxpool3s2_backward_ex(dy, arg, dx, None if sk is None else sk.to(DEV), lo if sk is not None else 0,
+                                   hi if sk is not None else 0)
+        torch.cuda.synchronize()
+        assert bool((buf[:guard] == sent).all()) and bool((buf[-guard:] == sent).all())
+        ref = want if sk is not None else plain.view(-1)
+        assert torch.equal(dx.cpu().view(-1).view(torch.int32), ref.view(torch.int32))
+
+
 @pytest.mark.parametrize("shape", [(12, 16, 64, 208), (2, 256, 4, 13), (2, 3, 1, 1), (1, 2, 1, 5),
                                    (2, 2, 2, 2), (3, 4, 3, 7)])
 def test_upsample2(shape):
