@@ -60,8 +60,8 @@ typedef struct md2_loss_cfg {
   int c;                       /* image channels (1 or 3)                                    */
   int width, height;           /* Params.target_size                                         */
   int nscales;                 /* length(TrainCache.scales)                                  */
-  int scale_w[MD2_MAX_SCALES]; /* disparity resolution of each scale                         */
-  int scale_h[MD2_MAX_SCALES];
+  int scale_w[MD2_MAX_SCALES]; /* disparity resolution of each scale: 2 <= scale_w <= width, */
+  int scale_h[MD2_MAX_SCALES]; /* 1 <= scale_h <= height (else MD2_EINVAL)                   */
   float smooth_weight[MD2_MAX_SCALES]; /* train_loss: disparity_smoothness * scale           */
   float divisor;               /* train_loss: nscales (training.jl:77); slow_depth: 1         */
   int smooth_normalize;        /* 1: disparity / (mean + 1e-7) (training.jl:64-65)           */

@@ -36,6 +36,16 @@ TailLayout layout(const LossTailCfg& c) {
 }
 
 inline float ratio(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+
+// A one-row disparity map is upsampled like any other; a one-column map is not supported: the
+// photometric pass reads the two column taps of the upsample as one 8-byte pair.  Checked before
+// anything is launched.
+int check_scale_dims(const LossTailCfg& c) {
+  for (int s = 0; s < c.nscales; ++s)
+    MD2_CHECK_ARG(c.dw[s] >= 2 && c.dh[s] >= 1 && c.dw[s] <= c.W && c.dh[s] <= c.H,
+                  "scale dims: a disparity map must be 2..width columns by 1..height rows");
+  return MD2_OK;
+}
 }  // namespace
 
 size_t loss_tail_workspace_bytes(const LossTailCfg& c) { return layout(c).total; }
@@ -52,6 +62,7 @@ int loss_tail_run(const LossTailCfg& c, const float* const* disp, const float* p
   MD2_CHECK_ARG(c.C == 1 || c.C == 3, "channels must be 1 or 3");
   MD2_CHECK_ARG(workspace != nullptr && disp != nullptr && pose != nullptr && x != nullptr,
                 "null pointer");
+  MD2_TRY(check_scale_dims(c));
   const TailLayout L = layout(c);
   char* ws = (char*)workspace;
   float* Rt = (float*)(ws + L.Rt);
@@ -101,7 +112,6 @@ int loss_tail_run(const LossTailCfg& c, const float* const* disp, const float* p
   db.N = c.N;
   db.parts = MEAN_PARTS;
   for (int s = 0; s < c.nscales; ++s) {
-    MD2_CHECK_ARG(c.dw[s] >= 1 && c.dh[s] >= 1 && c.dw[s] <= c.W && c.dh[s] <= c.H, "scale dims");
     PhotoScale& ps = pa.sc[s];
     ps.disp = disp[s];
     ps.dw = c.dw[s];
@@ -252,8 +262,7 @@ int loss_tail_sources_run(const LossTailCfg& c, int S, const LossSource* src, co
   }
   MD2_CHECK_ARG(seen == (1 << n_learned) - 1,
                 "pose_block must be distinct and below the number of learned sources");
-  for (int s = 0; s < c.nscales; ++s)
-    MD2_CHECK_ARG(c.dw[s] >= 1 && c.dh[s] >= 1 && c.dw[s] <= c.W && c.dh[s] <= c.H, "scale dims");
+  MD2_TRY(check_scale_dims(c));
 
   float* loss = o.loss;
   const float* const* d_disp = o.d_disp;

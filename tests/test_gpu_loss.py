@@ -70,8 +70,14 @@ def _check(N, C, H, W, automask=False, seed=7, strict=True, near=False):
         disps = D.disparities(N, H, W, seed=seed + 4)
         poses = D.poses(N, seed=seed + 6)
     am = O.automasking_loss(x, x[:, 1], (1, 3)).detach() if automask else None
-    g = _gpu(disps, poses, x, K, invK, am)
-    _, _, _, per_src = _oracle(disps, poses, x, K, invK, am)
+    _check_inputs(disps, poses, x, K, invK, am)
+
+
+def _check_inputs(disps, poses, x, K, invK, am, smoothness=1e-3):
+    """The procedure of the module docstring on given inputs (tests/test_gpu_loss_smooth.py runs it
+    at a smoothness weight that makes both gradient passes comparable)."""
+    g = _gpu(disps, poses, x, K, invK, am, smoothness=smoothness)
+    _, _, _, per_src = _oracle(disps, poses, x, K, invK, am, smoothness=smoothness)
     forced = []
     for s in range(len(SCALES)):
         l0, l1 = per_src[s][0], per_src[s][1]
@@ -86,7 +92,7 @@ def _check(N, C, H, W, automask=False, seed=7, strict=True, near=False):
         mism = (sel != ref) & ~tie
         assert mism.sum().item() == 0, (s, mism.sum().item())
         forced.append(sel + (1 if am is not None else 0))
-    lo, dd_o, dp_o, _ = _oracle(disps, poses, x, K, invK, am, forced_sel=forced,
+    lo, dd_o, dp_o, _ = _oracle(disps, poses, x, K, invK, am, forced_sel=forced, smoothness=smoothness,
                                 forced_cells=g["vis_cell"])
     assert abs(g["loss"].item() - lo.item()) <= 2e-5 * abs(lo.item()), (g["loss"].item(), lo.item())
     tol_d, tol_p = 2e-4, 2e-4
