@@ -53,8 +53,9 @@ struct PhotoArgs {
 };
 
 // The photometric pass over 1..MAX_SOURCES sources, each with its own base pointer and sample
-// stride (photo_sources.hip).  In its scales, partials rows are 1 + 12 nsrc floats (loss sum, then
-// dR(9) dt(3) per source), sel_map holds 0..nsrc-1 or -1, and cell_map is [nsrc][N][H][W].
+// stride (photo_sources.hip); also what the visualisation warp reads.  In its scales, partials
+// rows are 1 + 12 nsrc floats (loss sum, then dR(9) dt(3) per source), sel_map holds 0..nsrc-1 or
+// -1, and cell_map is [nsrc][N][H][W]: PhotoArgs' layout at nsrc = 2.
 constexpr int MAX_SOURCES = 3;
 struct PhotoSrcArgs {
   PhotoScale sc[MAX_SCALES];
@@ -141,32 +142,28 @@ struct FinalizeArgs {
   float divisor;                    // train_loss: nscales; slow_depth: 1
   int nscales;
   int N;
+  int nsrc;                         // photo_partials rows are 1 + 12 nsrc floats
 };
 
-// all a.nscales scales in one launch of photo_stream_kernel (photo.hip)
+// The two photometric launchers: the packed two-source kernel over frames of x (photo.hip) and
+// the scalar kernel over a.nsrc sources addressed by pointer (photo_sources.hip).  Both run all
+// a.nscales scales in one launch; the nsrc = 2 instance of the second gives the first's bits.
 int launch_photometric(const PhotoArgs& a, const Geom& g, int C, hipStream_t st);
-// identity-reprojection loss (training.jl:9-11): out [N][H][W] = min over the two raw sources of
-// photometric_loss(source, target)
-int launch_automask(const float* x, long x_sample_stride, long x_frame_stride, int target,
-                    int src0, int src1, int N, int C, int H, int W, float* out, hipStream_t st);
-// the same over a.nsrc sources (photo_sources.hip); the nsrc = 2 instance gives launch_photometric's
-// bits and is not on the two-source path
 int launch_photometric_sources(const PhotoSrcArgs& a, const Geom& g, int C, hipStream_t st);
-// min over nsrc raw sources (pointer + sample stride each, [C][H][W] frames) of
-// photometric_loss(source, target), first argmin on ties; two sources give launch_automask's bits
+// their shared launch-time argument checks; *cells: the scales carry cell maps
+int check_photometric(const PhotoScale* sc, int nscales, const Geom& g, int C, bool* cells);
+// identity-reprojection loss (training.jl:9-11): out [N][H][W] = min over nsrc raw sources
+// (pointer + sample stride each, [C][H][W] frames) of photometric_loss(source, target), first
+// argmin on ties
 int launch_automask_sources(const float* target, long target_sample_stride, const float* const* src,
                             const long* src_sample_stride, int nsrc, int N, int C, int H, int W,
                             float* out, hipStream_t st);
-// out [nsrc][N][C][H][W]
-int launch_warp_vis_sources(const PhotoSrcArgs& a, int scale, const Geom& g, int C, float* out,
-                            hipStream_t st);
-// launch_loss_finalize / launch_pose_grad_reduce over partials rows of 1 + 12 nsrc floats;
-// dRt [nsrc * N][12]
-int launch_loss_finalize_sources(const FinalizeArgs& a, int nsrc, float* dRt, float* loss,
-                                 hipStream_t st);
-int launch_pose_grad_reduce_sources(const FinalizeArgs& a, int nsrc, float* dRt, hipStream_t st);
-// warped sources only (train_loss vis_warped): out [2][N][C][H][W]
-int launch_warp_vis(const PhotoArgs& a, int scale, const Geom& g, int C, float* out, hipStream_t st);
+// the same over two source frames of x
+int launch_automask(const float* x, long x_sample_stride, long x_frame_stride, int target,
+                    int src0, int src1, int N, int C, int H, int W, float* out, hipStream_t st);
+// warped sources only (train_loss vis_warped): out [nsrc][N][C][H][W]
+int launch_warp_vis(const PhotoSrcArgs& a, int scale, const Geom& g, int C, float* out,
+                    hipStream_t st);
 // partial rows per scale of the photometric pass run with `nscales` scales
 long photometric_blocks(int W, int H, int N, int nscales);
 long smooth_blocks(int W, int H, int N);
@@ -174,8 +171,9 @@ long smooth_blocks(int W, int H, int N);
 int launch_disp_sum(const DispSumBatch& b, int nscales, hipStream_t st);
 int launch_smooth(const SmoothArgs* a, int nscales, int C, hipStream_t st);
 int launch_up_adjoint(const UpAdjArgs* a, int nscales, hipStream_t st);
+// the reductions read partials rows of 1 + 12 a.nsrc floats; dRt [nsrc * N][12] or nullptr
 int launch_loss_finalize(const FinalizeArgs& a, float* dRt, float* loss, hipStream_t st);
-// per-(source, sample) sums of the photometric blocks' pose partials -> dRt [2N][12]
+// per-(source, sample) sums of the photometric blocks' pose partials -> dRt [nsrc * N][12]
 int launch_pose_grad_reduce(const FinalizeArgs& a, float* dRt, hipStream_t st);
 int launch_so3_fwd(const float* pose, int count, int N, int invert_mask, float* Rt,
                    hipStream_t st);

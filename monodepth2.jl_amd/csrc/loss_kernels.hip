@@ -312,10 +312,10 @@ __global__ __launch_bounds__(256) void up_adjoint_kernel(UpAdjBatch b) {
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void loss_finalize_kernel(FinalizeArgs a) {
   __shared__ float red[4 * 2];
-  // one block per scale: sum photometric (col 0 of 25) and smooth (col 0 of 2) partials
-  const int s = blockIdx.x;
+  // one block per scale: sum photometric (col 0 of 1 + 12 nsrc) and smooth (col 0 of 2) partials
+  const int s = blockIdx.x, ps = 1 + 12 * a.nsrc;
   float v[2] = {0.f, 0.f};
-  for (long k = threadIdx.x; k < a.photo_blocks[s]; k += 256) v[0] += a.photo_partials[s][k * 25];
+  for (long k = threadIdx.x; k < a.photo_blocks[s]; k += 256) v[0] += a.photo_partials[s][k * ps];
   for (long k = threadIdx.x; k < a.smooth_blocks[s]; k += 256) v[1] += a.smooth_partials[s][k * 2];
   block_sum256<2>(v, red);
   if (threadIdx.x == 0) {
@@ -332,20 +332,21 @@ __global__ void loss_total_kernel(const float* terms, int nscales, float divisor
   }
 }
 
-// grid: (2*N) blocks; sums the 24 pose values of every block of image n over all scales.
+// grid: (nsrc*N) blocks; block q = s*N + n sums the 12 pose values of source s over every block of
+// image n and every scale -> dRt [nsrc*N][12]
 __global__ __launch_bounds__(256) void pose_grad_reduce_kernel(FinalizeArgs a, float* dRt) {
   __shared__ float red[4 * 12];
-  const int q = blockIdx.x;            // q = s*N + n
+  const int q = blockIdx.x, ps = 1 + 12 * a.nsrc;
   const int s = q / a.N, n = q % a.N;
   float v[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) v[k] = 0.f;
   for (int sc = 0; sc < a.nscales; ++sc) {
     const long per = a.photo_blocks[sc] / a.N;
-    const float* p = a.photo_partials[sc] + (long)n * per * 25;
+    const float* p = a.photo_partials[sc] + (long)n * per * ps;
     for (long b = threadIdx.x; b < per; b += 256) {
 #pragma unroll
-      for (int k = 0; k < 12; ++k) v[k] += p[b * 25 + 1 + 12 * s + k];
+      for (int k = 0; k < 12; ++k) v[k] += p[b * ps + 1 + 12 * s + k];
     }
   }
   block_sum256<12>(v, red);
@@ -494,57 +495,6 @@ __global__ void so3_bwd_kernel(const float* __restrict__ pose, int count, int N,
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-// Visualisation warp (train_loss vis_warped, src/training.jl:48-57,71-73): both sources
-// resampled through the scale's depth and pose, no loss, no backward.  One thread per target
-// pixel, all C channels of both sources; same geometry helpers as the photometric kernel.
-template <int C>
-__global__ __launch_bounds__(256) void warp_vis_kernel(PhotoArgs a, int scale, Geom g, float* __restrict__ out) {
-  const PhotoScale sc = a.sc[scale];
-  const int HW = g.W * g.H;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long)a.N * HW) return;
-  const int n = (int)(idx / HW), pix = (int)(idx - (long)n * HW);
-  const int Y = pix / g.W, X = pix - Y * g.W;
-  const float d = disp_at(sc.disp + (long)n * sc.dw * sc.dh, sc.dw, sc.dh, sc.rx, sc.ry, g.W, g.H, X, Y);
-  const float depth = 1.f / (d * g.disp_range + g.min_disp);
-  float r0, r1, r2;
-  ray_at(g, X, Y, r0, r1, r2);
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    Proj p;
-    project_point(g, a.Rt + ((long)s * a.N + n) * 12, depth, r0, r1, r2, p);
-    const float x = fminf(fmaxf(p.ix, 0.f), (float)(g.W - 1));
-    const float y = fminf(fmaxf(p.iy, 0.f), (float)(g.H - 1));
-    const int x0 = (int)x, y0 = (int)y;
-    const int x1 = min(x0 + 1, g.W - 1), y1 = min(y0 + 1, g.H - 1);
-    const float fx = x - (float)x0, fy = y - (float)y0;
-    const float* src = a.x + (long)n * a.x_sample_stride + (long)(s ? a.src1 : a.src0) * a.x_frame_stride;
-    float* o = out + ((long)s * a.N + n) * C * HW + pix;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float* q = src + (long)c * HW;
-      const float v = (1.f - fy) * ((1.f - fx) * q[y0 * g.W + x0] + fx * q[y0 * g.W + x1]) +
-                      fy * ((1.f - fx) * q[y1 * g.W + x0] + fx * q[y1 * g.W + x1]);
-      o[(long)c * HW] = v;
-    }
-  }
-}
-
-int launch_warp_vis(const PhotoArgs& a, int scale, const Geom& g, int C, float* out, hipStream_t st) {
-  const long n = (long)a.N * g.W * g.H;
-  const dim3 grid((unsigned)cdiv(n, 256L));
-  if (C == 3)
-    hipLaunchKernelGGL(warp_vis_kernel<3>, grid, dim3(256), 0, st, a, scale, g, out);
-  else if (C == 1)
-    hipLaunchKernelGGL(warp_vis_kernel<1>, grid, dim3(256), 0, st, a, scale, g, out);
-  else {
-    set_error("warp_vis: channels must be 1 or 3");
-    return MD2_ENOTSUP;
-  }
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
-}
-
 long smooth_blocks(int W, int H, int N) { return (long)cdiv(W, SM_TW) * cdiv(H, SM_BR) * N; }
 
 int launch_disp_sum(const DispSumBatch& b, int nscales, hipStream_t st) {
@@ -593,20 +543,19 @@ int launch_up_adjoint(const UpAdjArgs* a, int nscales, hipStream_t st) {
 }
 
 int launch_loss_finalize(const FinalizeArgs& a, float* dRt, float* loss, hipStream_t st) {
+  MD2_CHECK_ARG(a.nsrc >= 1 && a.nsrc <= MAX_SOURCES, "loss_finalize: 1 to 3 sources");
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(a.nscales), dim3(256), 0, st, a);
   MD2_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_total_kernel, dim3(1), dim3(64), 0, st, a.terms, a.nscales, a.divisor,
                      loss);
   MD2_LAUNCH_CHECK();
-  if (dRt) {
-    hipLaunchKernelGGL(pose_grad_reduce_kernel, dim3(2 * a.N), dim3(256), 0, st, a, dRt);
-    MD2_LAUNCH_CHECK();
-  }
+  if (dRt) return launch_pose_grad_reduce(a, dRt, st);
   return MD2_OK;
 }
 
 int launch_pose_grad_reduce(const FinalizeArgs& a, float* dRt, hipStream_t st) {
-  hipLaunchKernelGGL(pose_grad_reduce_kernel, dim3(2 * a.N), dim3(256), 0, st, a, dRt);
+  MD2_CHECK_ARG(a.nsrc >= 1 && a.nsrc <= MAX_SOURCES, "pose_grad_reduce: 1 to 3 sources");
+  hipLaunchKernelGGL(pose_grad_reduce_kernel, dim3(a.nsrc * a.N), dim3(256), 0, st, a, dRt);
   MD2_LAUNCH_CHECK();
   return MD2_OK;
 }
@@ -627,11 +576,12 @@ int launch_so3_bwd(const float* pose, int count, int N, int invert_mask, const f
   return MD2_OK;
 }
 
-// Visualisation warp over S sources addressed by pointer (launch_warp_vis is the two-source form
-// over frames of x; same per-pixel arithmetic): out [S][N][C][H][W]
+// Visualisation warp (train_loss vis_warped, src/training.jl:48-57,71-73): every source resampled
+// through the scale's depth and pose, no loss, no backward.  One thread per target pixel, all C
+// channels of all S sources; same geometry helpers as the photometric kernels.  out [S][N][C][H][W]
 template <int C, int S>
-__global__ __launch_bounds__(256) void warp_vis_sources_kernel(PhotoSrcArgs a, int scale, Geom g,
-                                                               float* __restrict__ out) {
+__global__ __launch_bounds__(256) void warp_vis_kernel(PhotoSrcArgs a, int scale, Geom g,
+                                                       float* __restrict__ out) {
   const PhotoScale sc = a.sc[scale];
   const int HW = g.W * g.H;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -663,15 +613,15 @@ __global__ __launch_bounds__(256) void warp_vis_sources_kernel(PhotoSrcArgs a, i
   }
 }
 
-int launch_warp_vis_sources(const PhotoSrcArgs& a, int scale, const Geom& g, int C, float* out,
-                            hipStream_t st) {
+int launch_warp_vis(const PhotoSrcArgs& a, int scale, const Geom& g, int C, float* out,
+                    hipStream_t st) {
   MD2_CHECK_ARG(a.nsrc >= 1 && a.nsrc <= MAX_SOURCES, "warp_vis: 1 to 3 sources");
   const long n = (long)a.N * g.W * g.H;
   const dim3 grid((unsigned)cdiv(n, 256L));
   const int key = C * 10 + a.nsrc;
-#define MD2_WVS(C_, S_)                                                                              \
-  case C_ * 10 + S_:                                                                                 \
-    hipLaunchKernelGGL((warp_vis_sources_kernel<C_, S_>), grid, dim3(256), 0, st, a, scale, g, out); \
+#define MD2_WVS(C_, S_)                                                                      \
+  case C_ * 10 + S_:                                                                         \
+    hipLaunchKernelGGL((warp_vis_kernel<C_, S_>), grid, dim3(256), 0, st, a, scale, g, out); \
     break;
   switch (key) {
     MD2_WVS(1, 1) MD2_WVS(1, 2) MD2_WVS(1, 3) MD2_WVS(3, 1) MD2_WVS(3, 2) MD2_WVS(3, 3)
@@ -680,75 +630,6 @@ int launch_warp_vis_sources(const PhotoSrcArgs& a, int scale, const Geom& g, int
       return MD2_ENOTSUP;
   }
 #undef MD2_WVS
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Reductions over partials rows of 1 + 12 S floats (loss_kernels.hip has the 25-float forms; the
-// summation order is the same, so S = 2 gives the same bits)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void loss_finalize_sources_kernel(FinalizeArgs a, int ps) {
-  __shared__ float red[4 * 2];
-  const int s = blockIdx.x;
-  float v[2] = {0.f, 0.f};
-  for (long k = threadIdx.x; k < a.photo_blocks[s]; k += 256) v[0] += a.photo_partials[s][k * ps];
-  for (long k = threadIdx.x; k < a.smooth_blocks[s]; k += 256) v[1] += a.smooth_partials[s][k * 2];
-  block_sum256<2>(v, red);
-  if (threadIdx.x == 0) {
-    a.terms[2 * s + 0] = v[0] * a.photo_scale;
-    a.terms[2 * s + 1] = v[1] * a.smooth_scale[s];
-  }
-}
-
-__global__ void loss_total_sources_kernel(const float* terms, int nscales, float divisor, float* loss) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    float l = 0.f;
-    for (int s = 0; s < nscales; ++s) l += terms[2 * s] + terms[2 * s + 1];
-    loss[0] = l / divisor;
-  }
-}
-
-// grid: (S*N) blocks; block q = s*N + n sums the 12 pose values of source s over every block of
-// image n and every scale -> dRt [S*N][12]
-__global__ __launch_bounds__(256) void pose_grad_reduce_sources_kernel(FinalizeArgs a, int ps, float* dRt) {
-  __shared__ float red[4 * 12];
-  const int q = blockIdx.x;
-  const int s = q / a.N, n = q % a.N;
-  float v[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) v[k] = 0.f;
-  for (int sc = 0; sc < a.nscales; ++sc) {
-    const long per = a.photo_blocks[sc] / a.N;
-    const float* p = a.photo_partials[sc] + (long)n * per * ps;
-    for (long b = threadIdx.x; b < per; b += 256) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) v[k] += p[b * ps + 1 + 12 * s + k];
-    }
-  }
-  block_sum256<12>(v, red);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) dRt[(long)q * 12 + k] = v[k];
-  }
-}
-
-int launch_loss_finalize_sources(const FinalizeArgs& a, int nsrc, float* dRt, float* loss, hipStream_t st) {
-  MD2_CHECK_ARG(nsrc >= 1 && nsrc <= MAX_SOURCES, "loss_finalize: 1 to 3 sources");
-  const int ps = 1 + 12 * nsrc;
-  hipLaunchKernelGGL(loss_finalize_sources_kernel, dim3(a.nscales), dim3(256), 0, st, a, ps);
-  MD2_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_total_sources_kernel, dim3(1), dim3(64), 0, st, a.terms, a.nscales,
-                     a.divisor, loss);
-  MD2_LAUNCH_CHECK();
-  if (dRt) return launch_pose_grad_reduce_sources(a, nsrc, dRt, st);
-  return MD2_OK;
-}
-
-int launch_pose_grad_reduce_sources(const FinalizeArgs& a, int nsrc, float* dRt, hipStream_t st) {
-  MD2_CHECK_ARG(nsrc >= 1 && nsrc <= MAX_SOURCES, "pose_grad_reduce: 1 to 3 sources");
-  hipLaunchKernelGGL(pose_grad_reduce_sources_kernel, dim3(nsrc * a.N), dim3(256), 0, st, a,
-                     1 + 12 * nsrc, dRt);
   MD2_LAUNCH_CHECK();
   return MD2_OK;
 }

@@ -1,5 +1,6 @@
 // Host orchestration of the loss tail: composeT -> per scale {mean, warp+SSIM, smoothness,
-// upsample adjoint} -> deterministic reductions -> composeT/so3 backward.
+// upsample adjoint} -> deterministic reductions -> composeT/so3 backward.  One body runs both
+// entry points below; they differ in where the sources come from and in the photometric kernel.
 #pragma once
 #include "loss_kernels.h"
 
@@ -31,20 +32,23 @@ struct LossTailOut {
   float* d_pose;
   float* vis_loss;
   signed char* vis_sel;
-  float* vis_warped;                    // [2][N][C][H][W] warped sources at the last scale or nullptr
-  int* vis_cell;                        // [nscales][2][N][H][W] bilinear cells (diagnostics) or nullptr
+  float* vis_warped;                    // [nsrc][N][C][H][W] warped sources at the last scale or nullptr
+  int* vis_cell;                        // [nscales][nsrc][N][H][W] bilinear cells (diagnostics) or nullptr
   hipEvent_t* photo_events = nullptr;   // optional [2]: around the (all-scale) photometric launch
 };
 
-// disp[s]: [N][dh][dw] sigmoid outputs; pose: [2N][6] (rvec, tvec) per (source, sample);
-// x: frames; automask: [N][H][W] or nullptr.  dloss: upstream scalar gradient.
+// Two learned sources, frames c.src0 / c.src1 of x with pose blocks 0 and 1, on the packed
+// two-source photometric kernel (photo.hip).  disp[s]: [N][dh][dw] sigmoid outputs; pose: [2N][6]
+// (rvec, tvec) per (source, sample); x: frames; automask: [N][H][W] or nullptr.  dloss: upstream
+// scalar gradient.
 int loss_tail_run(const LossTailCfg& c, const float* const* disp, const float* pose,
                   const float* x, const float* automask, float dloss, const LossTailOut& o,
                   void* workspace, hipStream_t st);
 
 // The loss tail over 1..MAX_SOURCES sources, each LEARNED (its pose comes from the pose network
-// and gets a gradient) or FIXED (a caller-supplied transform, data).  c.target / src0 / src1 /
-// invert_mask / x_*_stride are not read.
+// and gets a gradient) or FIXED (a caller-supplied transform, data), on the photometric kernel over
+// sources (photo_sources.hip), nsrc = 2 included.  c.target / src0 / src1 / invert_mask /
+// x_*_stride are not read.
 struct LossSource {
   const float* frames;        // sample i's [C][H][W] frame at frames + i * sample_stride
   long sample_stride;
@@ -55,7 +59,9 @@ struct LossSource {
 size_t loss_tail_sources_workspace_bytes(const LossTailCfg& c, int nsrc);
 // pose: [n_learned * N][6] (may be nullptr without learned sources); o.d_pose [n_learned * N][6],
 // rows as in pose; o.vis_warped [nsrc][N][C][H][W]; o.vis_cell [nscales][nsrc][N][H][W];
-// o.vis_sel holds 0..nsrc-1 or -1.  The learned sources' pose blocks must be 0..n_learned-1, each once.
+// o.vis_sel holds 0..nsrc-1 or -1.  The learned sources' pose blocks must be 0..n_learned-1, each
+// once; with the learned sources first and in block order composeT writes and reads Rt / dRt in
+// place, any other order stages its rows through copies.
 int loss_tail_sources_run(const LossTailCfg& c, int nsrc, const LossSource* src, const float* target,
                           long target_sample_stride, const float* const* disp, const float* pose,
                           const float* automask, float dloss, const LossTailOut& o, void* workspace,

@@ -101,53 +101,15 @@ __global__ __launch_bounds__(256) void unorm8_kernel(const uint8_t* __restrict__
   }
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void automask_kernel(const float* __restrict__ x, long x_ss,
-                                                       long x_fs, int target, int src0, int src1,
-                                                       int W, int H, float* __restrict__ out) {
-  constexpr int RW = OT_W + 2, RH = OT_H + 2, NR = RW * RH;
-  __shared__ float s_t[C][NR], s_s[2][C][NR];
-  const int n = blockIdx.z, x0 = blockIdx.x * OT_W, y0 = blockIdx.y * OT_H;
-  const long HW = (long)W * H;
-  const float* xb = x + (long)n * x_ss;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    load_region<1>(xb + target * x_fs + c * HW, W, H, x0, y0, s_t[c]);
-    load_region<1>(xb + src0 * x_fs + c * HW, W, H, x0, y0, s_s[0][c]);
-    load_region<1>(xb + src1 * x_fs + c * HW, W, H, x0, y0, s_s[1][c]);
-  }
-  __syncthreads();
-  const int tx = threadIdx.x % OT_W, ty = threadIdx.x / OT_W;
-  const int gx = x0 + tx, gy = y0 + ty;
-  if (gx >= W || gy >= H) return;
-  int wi[9];
-  window_idx<1>(gx, gy, W, H, x0, y0, wi);
-  const int ci = (ty + 1) * RW + tx + 1;
-  float l[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float ss = 0.f, l1 = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const SsimWin w = ssim_window(s_s[s][c], s_t[c], wi, ci);
-      ss += fminf(fmaxf(w.val, 0.f), 1.f);
-      l1 += fabsf(s_t[c][ci] - s_s[s][c][ci]);
-    }
-    l[s] = 0.85f * (ss / (float)C) + 0.15f * (l1 / (float)C);
-  }
-  out[((long)n * H + gy) * W + gx] = l[1] < l[0] ? l[1] : l[0];   // first argmin on ties
-}
-
-// the same over S raw sources, each its own tensor (pointer + sample stride); S = 2 repeats
-// automask_kernel's arithmetic
+// S raw sources, each its own tensor (pointer + sample stride)
 struct AutomaskSrc {
   const float* src[MAX_SOURCES];
   long ss[MAX_SOURCES];
 };
 template <int C, int S>
-__global__ __launch_bounds__(256) void automask_sources_kernel(const float* __restrict__ target,
-                                                               long t_ss, AutomaskSrc a, int W, int H,
-                                                               float* __restrict__ out) {
+__global__ __launch_bounds__(256) void automask_kernel(const float* __restrict__ target, long t_ss,
+                                                       AutomaskSrc a, int W, int H,
+                                                       float* __restrict__ out) {
   constexpr int RW = OT_W + 2, RH = OT_H + 2, NR = RW * RH;
   __shared__ float s_t[C][NR], s_s[S][C][NR];
   const int n = blockIdx.z, x0 = blockIdx.x * OT_W, y0 = blockIdx.y * OT_H;
@@ -486,33 +448,16 @@ __global__ __launch_bounds__(256) void sample_mean_kernel(const float* __restric
   if (threadIdx.x == 0) out[blockIdx.x] = v[0] / (float)hw;
 }
 
-int launch_automask(const float* x, long x_sample_stride, long x_frame_stride, int target,
-                    int src0, int src1, int N, int C, int H, int W, float* out, hipStream_t st) {
-  const dim3 grid(cdiv(W, OT_W), cdiv(H, OT_H), N);
-  if (C == 3)
-    hipLaunchKernelGGL(automask_kernel<3>, grid, dim3(256), 0, st, x, x_sample_stride,
-                       x_frame_stride, target, src0, src1, W, H, out);
-  else if (C == 1)
-    hipLaunchKernelGGL(automask_kernel<1>, grid, dim3(256), 0, st, x, x_sample_stride,
-                       x_frame_stride, target, src0, src1, W, H, out);
-  else {
-    set_error("automask: channels must be 1 or 3");
-    return MD2_ENOTSUP;
-  }
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
-}
-
 namespace {
 template <int C>
 void automask_sources_c(const float* target, long t_ss, const AutomaskSrc& a, int nsrc, dim3 grid,
                         int W, int H, float* out, hipStream_t st) {
   if (nsrc == 1)
-    hipLaunchKernelGGL((automask_sources_kernel<C, 1>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
+    hipLaunchKernelGGL((automask_kernel<C, 1>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
   else if (nsrc == 2)
-    hipLaunchKernelGGL((automask_sources_kernel<C, 2>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
+    hipLaunchKernelGGL((automask_kernel<C, 2>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
   else
-    hipLaunchKernelGGL((automask_sources_kernel<C, 3>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
+    hipLaunchKernelGGL((automask_kernel<C, 3>), grid, dim3(256), 0, st, target, t_ss, a, W, H, out);
 }
 }  // namespace
 
@@ -538,6 +483,14 @@ int launch_automask_sources(const float* target, long target_sample_stride, cons
   }
   MD2_LAUNCH_CHECK();
   return MD2_OK;
+}
+
+int launch_automask(const float* x, long x_sample_stride, long x_frame_stride, int target,
+                    int src0, int src1, int N, int C, int H, int W, float* out, hipStream_t st) {
+  const float* src[2] = {x + src0 * x_frame_stride, x + src1 * x_frame_stride};
+  const long ss[2] = {x_sample_stride, x_sample_stride};
+  return launch_automask_sources(x + target * x_frame_stride, x_sample_stride, src, ss, 2, N, C, H, W,
+                                 out, st);
 }
 
 }  // namespace md2

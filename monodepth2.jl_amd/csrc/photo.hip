@@ -62,57 +62,20 @@
 //  * wave-uniform constants the row loop reads are pinned in VGPRs (vreg): the kernel is short
 //    of SGPRs, whose spills cost v_readlane restores in the loop, and has VGPRs to spare.
 #include <algorithm>
-#include <type_traits>
+#include <climits>
 
-#include "loss_kernels.h"
+#include "photo_device.h"
 
 namespace md2 {
 namespace {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-constexpr int PW = 60;            // output columns per wave
 constexpr int PHOTO_WAVES = 2048; // target tasks per launch: 2 waves per SIMD on 256 CUs
 
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2 bc(float s) { return (f2){s, s}; }
-__device__ __forceinline__ float from_left(float v) {    // lane i <- lane i-1 (lane 0 <- 0)
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float from_right(float v) {   // lane i <- lane i+1 (lane 63 <- 0)
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-// 3-lane window sums in the fixed order (v + left) + right, for NV values in two passes (header):
-// every DPP read stays NV instructions away from the write of its operand
-template <int NV>
-__device__ __forceinline__ void hsum3_n(float (&v)[NV]) {
-  float t[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) t[i] = v[i] + from_left(v[i]);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = t[i] + from_right(v[i]);
-}
-__device__ __forceinline__ int reflect_clamp(int i, int n) {
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
-}
-__device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-// a wave-uniform value pinned in a VGPR (header: the kernel is short of SGPRs)
-__device__ __forceinline__ float vreg(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
 __device__ __forceinline__ f2 frcp(f2 x) { return (f2){frcp(x.x), frcp(x.y)}; }
-
-template <int N_>
-using Slot = std::integral_constant<int, N_>;
-
-// which phases a row step runs (P1 always)
-constexpr int PH_P2 = 1, PH_P3 = 2, PH_ALL = 3;
 
 }  // namespace
 
@@ -624,51 +587,45 @@ long photometric_blocks(int W, int H, int N, int nscales) {
   return (long)photo_tiling(W, H, N, nscales).per_scale() * N;
 }
 
+int check_photometric(const PhotoScale* sc, int nscales, const Geom& g, int C, bool* cells) {
+  MD2_CHECK_ARG(nscales >= 1 && nscales <= MAX_SCALES, "photometric: nscales out of range");
+  MD2_CHECK_ARG(C == 1 || C == 3, "photometric: channels must be 1 or 3");
+  MD2_CHECK_ARG(g.W >= 3 && g.H >= 3, "photometric: image must be at least 3x3");
+  MD2_CHECK_ARG((long)C * g.W * g.H * 4 <= (long)INT_MAX, "photometric: frame exceeds 2 GiB");
+  *cells = false;
+  for (int s = 0; s < nscales; ++s) {
+    // the disparity column taps are one 8-byte pair load
+    MD2_CHECK_ARG(sc[s].dw >= 2, "photometric: disparity maps must be at least 2 columns wide");
+    MD2_CHECK_ARG(sc[s].disp && sc[s].g_disp && sc[s].partials, "photometric: null scale buffer");
+    *cells |= sc[s].cell_map != nullptr;
+  }
+  if (*cells) {
+    for (int s = 0; s < nscales; ++s)
+      MD2_CHECK_ARG(sc[s].cell_map != nullptr, "photometric: cell_map must be given for every scale or none");
+    MD2_CHECK_ARG(g.W <= PHOTO_CELL_MAXDIM && g.H <= PHOTO_CELL_MAXDIM,
+                  "photometric: cell_map packs 11-bit cells (w, h <= 2048)");
+  }
+  return MD2_OK;
+}
+
 int launch_photometric(const PhotoArgs& a, const Geom& g, int C, hipStream_t st) {
-  if (a.nscales < 1 || a.nscales > MAX_SCALES) {
-    set_error("photometric: nscales out of range");
-    return MD2_EINVAL;
-  }
-  if (g.W < 3 || g.H < 3) {
-    set_error("photometric: image must be at least 3x3");
-    return MD2_EINVAL;
-  }
-  for (int s = 0; s < a.nscales; ++s)
-    if (a.sc[s].dw < 2) {   // the disparity column taps are one 8-byte pair load
-      set_error("photometric: disparity maps must be at least 2 columns wide");
-      return MD2_EINVAL;
-    }
-  const PhotoTiling tl = photo_tiling(g.W, g.H, a.N, a.nscales);
-  const long blocks = tl.per_scale() * a.N * a.nscales;
   // CELLS: also record each owned pixel's bilinear cell / border state (sc.cell_map, parity
   // diagnostics).  A separate instantiation so the production kernel's registers are untouched;
   // the arithmetic is the same source, so values and decisions are the same.
-  bool cells = false;
-  for (int s = 0; s < a.nscales; ++s) cells |= a.sc[s].cell_map != nullptr;
-  if (cells) {
-    for (int s = 0; s < a.nscales; ++s)
-      if (!a.sc[s].cell_map) {
-        set_error("photometric: cell_map must be given for every scale or none");
-        return MD2_EINVAL;
-      }
-    if (g.W > PHOTO_CELL_MAXDIM || g.H > PHOTO_CELL_MAXDIM) {
-      set_error("photometric: cell_map packs 11-bit cells (w, h <= 2048)");
-      return MD2_EINVAL;
-    }
-  }
+  bool cells;
+  MD2_TRY(check_photometric(a.sc, a.nscales, g, C, &cells));
+  MD2_CHECK_ARG(a.x && a.Rt && a.N > 0, "photometric: null pointer");
+  const PhotoTiling tl = photo_tiling(g.W, g.H, a.N, a.nscales);
+  const long blocks = tl.per_scale() * a.N * a.nscales;
   const dim3 grid((unsigned)blocks), block(64);
   if (C == 3 && !cells)
     hipLaunchKernelGGL((photo_stream_kernel<3, false>), grid, block, 0, st, a, g, tl);
   else if (C == 3)
     hipLaunchKernelGGL((photo_stream_kernel<3, true>), grid, block, 0, st, a, g, tl);
-  else if (C == 1 && !cells)
+  else if (!cells)
     hipLaunchKernelGGL((photo_stream_kernel<1, false>), grid, block, 0, st, a, g, tl);
-  else if (C == 1)
+  else
     hipLaunchKernelGGL((photo_stream_kernel<1, true>), grid, block, 0, st, a, g, tl);
-  else {
-    set_error("photometric: channels must be 1 or 3");
-    return MD2_ENOTSUP;
-  }
   MD2_LAUNCH_CHECK();
   return MD2_OK;
 }

@@ -19,52 +19,9 @@
 //    the 2 waves per SIMD the S <= 2 instances ask for, 8 waves of a CU hold at most 80 KB of the
 //    160 KB; the S = 3 instances ask for one wave per SIMD (they need the registers), 58 KB.
 // Built with photo.hip's flags (no implicit contraction; every FMA here is an explicit fmaf).
-#include <algorithm>
-#include <climits>
-#include <type_traits>
-
-#include "loss_kernels.h"
+#include "photo_device.h"
 
 namespace md2 {
-namespace {
-
-constexpr int PW = 60;            // output columns per wave (photo_tiling)
-
-__device__ __forceinline__ float from_left(float v) {    // lane i <- lane i-1 (lane 0 <- 0)
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float from_right(float v) {   // lane i <- lane i+1 (lane 63 <- 0)
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
-}
-// 3-lane window sums in the fixed order (v + left) + right, in two passes (photo.hip header)
-template <int NV>
-__device__ __forceinline__ void hsum3_n(float (&v)[NV]) {
-  float t[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) t[i] = v[i] + from_left(v[i]);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = t[i] + from_right(v[i]);
-}
-__device__ __forceinline__ int reflect_clamp(int i, int n) {
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
-}
-__device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float vreg(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-template <int N_>
-using Slot = std::integral_constant<int, N_>;
-
-constexpr int PH_P2 = 1, PH_P3 = 2, PH_ALL = 3;
-
-}  // namespace
 
 template <int C, int S, bool CELLS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 3 ? 1 : 2)))
@@ -574,27 +531,12 @@ void launch_c(const PhotoSrcArgs& a, const Geom& g, const PhotoTiling& tl, bool 
 
 int launch_photometric_sources(const PhotoSrcArgs& a, const Geom& g, int C, hipStream_t st) {
   MD2_CHECK_ARG(a.nsrc >= 1 && a.nsrc <= MAX_SOURCES, "photometric: 1 to 3 sources");
-  MD2_CHECK_ARG(a.nscales >= 1 && a.nscales <= MAX_SCALES, "photometric: nscales out of range");
-  MD2_CHECK_ARG(C == 1 || C == 3, "photometric: channels must be 1 or 3");
-  MD2_CHECK_ARG(g.W >= 3 && g.H >= 3, "photometric: image must be at least 3x3");
-  MD2_CHECK_ARG((long)C * g.W * g.H * 4 <= (long)INT_MAX, "photometric: frame exceeds 2 GiB");
+  bool cells;
+  MD2_TRY(check_photometric(a.sc, a.nscales, g, C, &cells));
   MD2_CHECK_ARG(a.target && a.Rt && a.N > 0, "photometric: null pointer");
   for (int s = 0; s < a.nsrc; ++s) MD2_CHECK_ARG(a.src[s] != nullptr, "photometric: null source");
-  for (int s = 0; s < a.nscales; ++s) {
-    // the disparity column taps are one 8-byte pair load
-    MD2_CHECK_ARG(a.sc[s].dw >= 2, "photometric: disparity maps must be at least 2 columns wide");
-    MD2_CHECK_ARG(a.sc[s].disp && a.sc[s].g_disp && a.sc[s].partials, "photometric: null scale buffer");
-  }
   const PhotoTiling tl = photo_tiling(g.W, g.H, a.N, a.nscales);
   const long blocks = tl.per_scale() * a.N * a.nscales;
-  bool cells = false;
-  for (int s = 0; s < a.nscales; ++s) cells |= a.sc[s].cell_map != nullptr;
-  if (cells) {
-    for (int s = 0; s < a.nscales; ++s)
-      MD2_CHECK_ARG(a.sc[s].cell_map != nullptr, "photometric: cell_map must be given for every scale or none");
-    MD2_CHECK_ARG(g.W <= PHOTO_CELL_MAXDIM && g.H <= PHOTO_CELL_MAXDIM,
-                  "photometric: cell_map packs 11-bit cells (w, h <= 2048)");
-  }
   if (C == 3)
     launch_c<3>(a, g, tl, cells, blocks, st);
   else

@@ -152,6 +152,36 @@ def stereo_sources(x, x_stereo, stereo_Rt, cache: TrainCache, temporal=True):
     return arr, k + 1, k
 
 
+def _results(disparities, x, nsrc, n_learned, grads, visualize):
+    """The result dict of a loss-tail call over ``nsrc`` sources, ``n_learned`` of them learned, and
+    the ``md2_loss_out`` that points into it."""
+    import torch
+    N, L, C_, H, W = x.shape
+    dev, ns = x.device, len(disparities)
+    res = {"loss": torch.empty(1, dtype=torch.float32, device=dev),
+           "terms": torch.empty(ns, 2, dtype=torch.float32, device=dev),
+           "d_disp": [torch.empty_like(d) for d in disparities] if grads else [None] * ns,
+           "d_pose": (torch.empty(n_learned * N, 6, dtype=torch.float32, device=dev)
+                      if grads and n_learned > 0 else None)}
+    if visualize:
+        res["vis_loss"] = torch.empty(ns, N, H, W, dtype=torch.float32, device=dev)
+        res["vis_sel"] = torch.empty(ns, N, H, W, dtype=torch.int8, device=dev)
+        res["vis_warped"] = torch.empty(nsrc, N, C_, H, W, dtype=torch.float32, device=dev)
+        # per-pixel bilinear cells / border states of every source (parity diagnostics)
+        res["vis_cell"] = torch.empty(ns, nsrc, N, H, W, dtype=torch.int32, device=dev)
+    out = _lib.LossOut()
+    out.loss = res["loss"].data_ptr()
+    out.terms = res["terms"].data_ptr()
+    for i, d in enumerate(res["d_disp"]):
+        out.d_disp[i] = None if d is None else d.data_ptr()
+    out.d_pose = None if res["d_pose"] is None else res["d_pose"].data_ptr()
+    out.vis_loss = res["vis_loss"].data_ptr() if visualize else None
+    out.vis_sel = res["vis_sel"].data_ptr() if visualize else None
+    out.vis_warped = res["vis_warped"].data_ptr() if visualize else None
+    out.vis_cell = res["vis_cell"].data_ptr() if visualize else None
+    return res, out
+
+
 def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Params, *,
               grads=True, smooth_weights=None, divisor=None, smooth_normalize=True,
               dloss=1.0, sigmoid_grad=False, visualize=False, keep_workspace=False,
@@ -192,34 +222,15 @@ def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Param
     pose = pack_poses(poses).to(dev, torch.float32)
     ws_bytes = lib().md2_loss_workspace_size(C.byref(cfg))
     ws = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev)
-    res = {"loss": torch.empty(1, dtype=torch.float32, device=dev),
-           "terms": torch.empty(len(disparities), 2, dtype=torch.float32, device=dev),
-           "d_disp": [torch.empty_like(d) for d in disparities] if grads else [None] * len(disparities),
-           "d_pose": torch.empty(2 * N, 6, dtype=torch.float32, device=dev) if grads else None}
+    res, out = _results(disparities, x, 2, 2, grads, visualize)
     if keep_workspace:
         res["workspace"] = ws
-    if visualize:
-        res["vis_loss"] = torch.empty(len(disparities), N, H, W, dtype=torch.float32, device=dev)
-        res["vis_sel"] = torch.empty(len(disparities), N, H, W, dtype=torch.int8, device=dev)
-        res["vis_warped"] = torch.empty(2, N, C_, H, W, dtype=torch.float32, device=dev)
-        # per-pixel bilinear cells / border states of both sources (parity diagnostics)
-        res["vis_cell"] = torch.empty(len(disparities), 2, N, H, W, dtype=torch.int32, device=dev)
     am = None
     if params.automasking:
         if auto_loss is None:        # automasking_loss(ssim, x, target; source_ids), on the GPU
             from .primitives import automasking_loss
             auto_loss = automasking_loss(x, cache.target_id, cache.source_ids)
         am = auto_loss.contiguous()
-    out = _lib.LossOut()
-    out.loss = res["loss"].data_ptr()
-    out.terms = res["terms"].data_ptr()
-    for i, d in enumerate(res["d_disp"]):
-        out.d_disp[i] = None if d is None else d.data_ptr()
-    out.d_pose = None if res["d_pose"] is None else res["d_pose"].data_ptr()
-    out.vis_loss = res["vis_loss"].data_ptr() if visualize else None
-    out.vis_sel = res["vis_sel"].data_ptr() if visualize else None
-    out.vis_warped = res["vis_warped"].data_ptr() if visualize else None
-    out.vis_cell = res["vis_cell"].data_ptr() if visualize else None
     disp_arr = ptr_array(disparities)
     check(lib().md2_loss_fwd_bwd(C.byref(cfg), C.cast(disp_arr, _lib.FP), ptr(pose), ptr(x), ptr(am),
                                  C.c_float(dloss), C.byref(out), ptr(ws), stream_of(dev)),
@@ -250,19 +261,9 @@ def run_loss_sources(disparities, pose, x, target, target_stride, sources, nsrc,
                        divisor=divisor, smooth_normalize=smooth_normalize, L=L, sigmoid_grad=sigmoid_grad)
     ws_bytes = lib().md2_loss_sources_workspace_size(C.byref(cfg), nsrc)
     ws = torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev)
-    ns = len(disparities)
-    res = {"loss": torch.empty(1, dtype=torch.float32, device=dev),
-           "terms": torch.empty(ns, 2, dtype=torch.float32, device=dev),
-           "d_disp": [torch.empty_like(d) for d in disparities] if grads else [None] * ns,
-           "d_pose": (torch.empty(n_learned * N, 6, dtype=torch.float32, device=dev)
-                      if grads and n_learned > 0 else None)}
+    res, out = _results(disparities, x, nsrc, n_learned, grads, visualize)
     if keep_workspace:
         res["workspace"] = ws
-    if visualize:
-        res["vis_loss"] = torch.empty(ns, N, H, W, dtype=torch.float32, device=dev)
-        res["vis_sel"] = torch.empty(ns, N, H, W, dtype=torch.int8, device=dev)
-        res["vis_warped"] = torch.empty(nsrc, N, C_, H, W, dtype=torch.float32, device=dev)
-        res["vis_cell"] = torch.empty(ns, nsrc, N, H, W, dtype=torch.int32, device=dev)
     am = None
     if params.automasking:
         if auto_loss is None:
@@ -274,16 +275,6 @@ def run_loss_sources(disparities, pose, x, target, target_stride, sources, nsrc,
             am = auto_loss.contiguous()
             if tuple(am.shape) != (N, 1, H, W) or am.dtype != torch.float32 or am.device != dev:
                 raise ValueError(f"auto_loss must be float32 [N,1,H,W] = {(N, 1, H, W)} on {dev}")
-    out = _lib.LossOut()
-    out.loss = res["loss"].data_ptr()
-    out.terms = res["terms"].data_ptr()
-    for i, d in enumerate(res["d_disp"]):
-        out.d_disp[i] = None if d is None else d.data_ptr()
-    out.d_pose = None if res["d_pose"] is None else res["d_pose"].data_ptr()
-    out.vis_loss = res["vis_loss"].data_ptr() if visualize else None
-    out.vis_sel = res["vis_sel"].data_ptr() if visualize else None
-    out.vis_warped = res["vis_warped"].data_ptr() if visualize else None
-    out.vis_cell = res["vis_cell"].data_ptr() if visualize else None
     disp_arr = ptr_array(disparities)
     check(lib().md2_loss_fwd_bwd_sources(C.byref(cfg), nsrc, sources, C.c_void_p(target), target_stride,
                                          C.cast(disp_arr, _lib.FP), ptr(pose), ptr(am), C.c_float(dloss),

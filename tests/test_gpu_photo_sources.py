@@ -256,6 +256,39 @@ def test_d_pose_shape_and_the_fixed_transform_is_read():
         assert torch.equal(u, v)
 
 
+def test_ms_with_the_stereo_source_first_gives_the_same_values():
+    """The same three sources in the order (stereo, src0 block 0, src1 block 1): not learned-first, so
+    the learned Rt / dRt rows are staged through copies.  The depth cotangent sums its sources in
+    the order given, so values, not bits: this file's bounds.  d_pose is in pose-block order."""
+    import md2hip
+    from md2hip import _lib
+    from md2hip import loss as L
+    N, Cc, H, W = 2, 3, 32, 64
+    x3, xs, K, invK, disps, poses, tx = _stereo_inputs(N, Cc, H, W, False)
+    cache, params = _cache_params(K, invK, W, H, N, len(disps), False)
+    dd = [d.float().to(DEV).contiguous() for d in disps]
+    pp = [(a.float().to(DEV), b.float().to(DEV)) for a, b in poses]
+    x, xst, Rt = x3.float().to(DEV).contiguous(), xs.float().to(DEV).contiguous(), _stereo_Rt(tx)
+    want = md2hip.loss_tail(dd, pp, x, None, cache, params, x_stereo=xst, stereo_Rt=Rt)
+    fs = Cc * H * W
+    arr = (_lib.LossSource * _lib.MAX_SOURCES)()
+    arr[0].frames, arr[0].sample_stride, arr[0].pose_block, arr[0].Rt = xst.data_ptr(), fs, -1, Rt.data_ptr()
+    for s, sid in enumerate(cache.source_ids):
+        arr[1 + s].frames, arr[1 + s].sample_stride = x.data_ptr() + 4 * (sid - 1) * fs, 3 * fs
+        arr[1 + s].pose_block, arr[1 + s].invert = s, int(sid < cache.target_id)
+    got = L.run_loss_sources(dd, md2hip.pack_poses(pp), x, x.data_ptr() + 4 * fs, 3 * fs, arr, 3, 2, None,
+                             cache, params)
+    torch.cuda.synchronize()
+    rel = abs(got["loss"].item() - want["loss"].item()) / abs(want["loss"].item())
+    errs = [D.rel_err(u.cpu(), v.cpu()) for u, v in zip(got["d_disp"], want["d_disp"])]
+    ep = D.rel_err(got["d_pose"].cpu(), want["d_pose"].cpu())
+    print(f"loss rel {rel:.3e}, d_disp rel {['%.3e' % e for e in errs]}, d_pose rel {ep:.3e}")
+    assert rel <= 2e-5, (got["loss"].item(), want["loss"].item())
+    for s, e in enumerate(errs):
+        assert e < 2e-4, (s, e)
+    assert got["d_pose"].shape == (2 * N, 6) and ep < 2e-4, ep
+
+
 def test_loss_tail_refuses_a_malformed_stereo_source():
     import md2hip
     N, Cc, H, W = 2, 3, 32, 64

@@ -11,7 +11,10 @@ Each repeat is a window of `--calls` back-to-back calls (`--steps` steps) betwee
 the variants alternate window by window, and the reported time is the median over `--repeats` windows
 after warm-up, with the minimum and maximum beside it.  Prints ONE JSON line:
 
-    python tools/bench_stereo.py [--repeats 20] [--calls 20] [--steps 10] > profiles/<tag>_stereo.json
+    python tools/bench_stereo.py [--repeats 20] [--calls 20] [--steps 10] [--automask] > profiles/<tag>_stereo.json
+
+--automask: Params(automasking=True) -- the tail rows and the step rows then also compute the
+identity-reprojection mask over their sources.
 """
 import argparse
 import json
@@ -59,6 +62,7 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--automask", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -74,7 +78,7 @@ def main():
     Rt = torch.from_numpy(md2hip.stereo_transforms(["l", "r"] * (N // 2), [False, False, True, True] * (N // 4))).to(dev)
     K, invK = md2hip.depth10k_intrinsics(W, H)
     cache = md2hip.TrainCache(K=K, invK=invK, scales=SCALES)
-    prm = md2hip.Params(target_size=(W, H), batch_size=N, automasking=False, disparity_smoothness=1e-3)
+    prm = md2hip.Params(target_size=(W, H), batch_size=N, automasking=args.automask, disparity_smoothness=1e-3)
 
     # (a) the loss tail on fixed inputs
     g = torch.Generator().manual_seed(11)
@@ -103,6 +107,8 @@ def main():
     result = {"tool": "bench_stereo", "device": torch.cuda.get_device_name(0), "batch": [N, 3, C, H, W],
               "scales": len(SCALES), "repeats": args.repeats, "calls_per_window": args.calls,
               "steps_per_window": args.steps, "loss_tail": tsum, "sources_S2_equals_packed_bits": same}
+    if args.automask:
+        result["automask"] = True
     base = tsum["packed_S2"]["median_ms"]
     result["loss_tail_over_packed"] = {k: round(v["median_ms"] / base, 3) for k, v in tsum.items()}
 

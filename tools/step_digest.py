@@ -5,10 +5,13 @@ parameters, the flat gradient and the BatchNorm running statistics.  Run it once
 re-rounds (different digest).
 
     python tools/step_digest.py [B] [steps] [--height H] [--width W] [--graph] [--guard MAXNORM]
+                                [--automask] [--stereo MS|S]
 
 --graph runs the captured step (train_step_graph) instead of the eager one; --guard MAXNORM uses a
 guarded optimiser (ADAM(max_grad_norm=MAXNORM)) and also prints its guard_state() after the last
-step."""
+step; --automask sets Params(automasking=True), so the model computes the identity-reprojection
+mask itself; --stereo MS|S adds a seeded stereo frame with stereo_transforms (as
+tools/bench_stereo.py builds them), beside the temporal sources (MS) or alone (S)."""
 import argparse
 import hashlib
 import json
@@ -27,6 +30,8 @@ def main():
     ap.add_argument("--width", type=int, default=416)
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--guard", type=float, default=None, metavar="MAXNORM")
+    ap.add_argument("--automask", action="store_true")
+    ap.add_argument("--stereo", choices=("MS", "S"), default=None)
     a = ap.parse_args()
     B, steps, H, W = a.B, a.steps, a.height, a.width
     import torch
@@ -40,17 +45,23 @@ def main():
                          md2hip.PoseDecoder(512), device=dev, seed=42)
     K, invK = md2hip.depth10k_intrinsics(W, H)
     cache = md2hip.TrainCache(K=K, invK=invK, scales=(0.125, 0.25, 0.5, 1.0))
-    params = md2hip.Params(target_size=(W, H), batch_size=B, automasking=False, disparity_smoothness=1e-3)
+    params = md2hip.Params(target_size=(W, H), batch_size=B, automasking=a.automask, disparity_smoothness=1e-3)
     opt = md2hip.ADAM(1e-4) if a.guard is None else md2hip.ADAM(1e-4, max_grad_norm=a.guard)
     x = md2hip.dist.synthetic_triplets(B, H, W, 0, dev)
+    stereo = {}
+    if a.stereo:
+        sides, flips = ["l", "r"] * B, [False, False, True, True] * B
+        stereo = dict(x_stereo=md2hip.dist.synthetic_triplets(B, H, W, 1, dev)[:, 0].contiguous(),
+                      stereo_Rt=torch.from_numpy(md2hip.stereo_transforms(sides[:B], flips[:B])).to(dev),
+                      temporal=a.stereo == "MS")
     ex = model.executor(tuple(x.shape), cache, params)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     losses = []
     for _ in range(steps):
         if a.graph:
-            ex.train_step_graph(x, opt, loss=loss)
+            ex.train_step_graph(x, opt, loss=loss, **stereo)
         else:
-            md2hip.dist.train_step(ex, model, opt, x, loss=loss)
+            md2hip.dist.train_step(ex, model, opt, x, loss=loss, **stereo)
         torch.cuda.synchronize()
         losses.append(loss.item())
 
@@ -62,6 +73,10 @@ def main():
         out["height"], out["width"] = H, W
     if a.graph:
         out["graph"] = True
+    if a.automask:
+        out["automask"] = True
+    if a.stereo:
+        out["stereo"] = a.stereo
     if a.guard is not None:
         out["guard"] = a.guard
         out["guard_state"] = opt.guard_state()
