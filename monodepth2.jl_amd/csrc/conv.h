@@ -68,18 +68,8 @@ struct ConvWorkspace {
   size_t bytes = 0;
 };
 
-// GEMM reduction order.  Tap-major (k = tap*C + c, tap = kh*KW + kw) keeps the filter tap
-// constant over a K chunk, so the spatial gather address is computed once per chunk and every
-// channel step is a scalar offset; it needs the channel count (and a concat split) to be a
-// multiple of the chunk.  Otherwise (the 3-channel stem, 1-channel disparity heads) the order is
-// channel-major k = c*KK + tap.  mode: 0 forward (C = Cin), 1 dgrad (C = Cout), 2 wgrad columns.
-bool conv_tap_major(const ConvShape& s, int mode);
-// forward (mode 0) / dgrad (mode 1) run the k-contiguous kernel with packed layout 1
-bool conv_px2_used(const ConvShape& s, int mode);
-bool conv_px3_used(const ConvShape& s, int mode);    // conv_px2 shapes + 32-row stride-1 forwards on the bf16x6 kernel
-bool conv_px16_used(const ConvShape& s, int mode);   // M <= 16 (16x16x4 MFMA kernel)
-
-// packed operand sizes (elements) -- weights are repacked K-major with zero padding
+// packed operand sizes (elements) -- weights are repacked K-major with zero padding, in the K
+// order and layout of the kernel the pass's route names (conv_plan.h PxRoute)
 size_t conv_fwd_packed_elems(const ConvShape& s);
 size_t conv_dgrad_packed_elems(const ConvShape& s);
 int conv_pack_fwd(const ConvShape& s, const float* w, float* packed, hipStream_t st);
@@ -91,7 +81,7 @@ int conv_pack_dgrad(const ConvShape& s, const float* w, float* packed, hipStream
 // (conv_pack_zero), not per update.
 struct PackDst {
   float* out;          // nullptr: not packed
-  int tap;             // tap-major K order (conv_tap_major)
+  int tap;             // tap-major K order (k = tap*C + c; else channel-major k = c*KK + tap)
   int layout;          // 0: [Kpad][Mpad]; 1: [Kpad/16][Mpad][16] (k-contiguous chunks, conv_px2)
   int Mpad;
 };

@@ -110,176 +110,188 @@ __global__ __launch_bounds__(256) void fold_reflect4_kernel(const float* __restr
   *reinterpret_cast<float4*>(dst) = r4;
 }
 
+// PX_HEAD: the batched kernel where this call's alignment and store mode fit it
+static int dgrad_head(const ConvShape& s, const PxRoute& r, const float* dy, const float* wpacked_d,
+                      const TensorOut& dx, hipStream_t st) {
+  MD2_CHECK_ARG(r.layout == 0 && !r.tap, "head: packed layout");
+  conv_arith_ref() = 0;
+  HeadJob j = conv_head_job(s);
+  j.wd = conv_head_w(s, 1, wpacked_d);
+  j.dy = dy;
+  j.dx = dx.p0;
+  j.dxbs = dx.bs0;
+  if (s.reflect && !dx.accumulate && !heads_job_unfit(j)) {
+    conv_note_kernel("head_batched");
+    return heads_bwd(&j, 1, nullptr, 0, st);
+  }
+  conv_note_kernel("head_fallback");
+  return head_dgrad(j, s.reflect, dx.accumulate, st);
+}
+
+// PX_REFLECT_HALO: the full adjoint on the padded grid (split-K slabs first in the workspace, the
+// padded image after them), then pad_reflect's adjoint into dX
+static int dgrad_reflect_halo(const ConvShape& s, const PxRoute& r, const ConvArgs& a, const TensorOut& dx,
+                              ConvWorkspace ws, hipStream_t st) {
+  const ConvShape& e = r.ext;
+  const HaloPlan& h = r.halo;
+  const long Ne = (long)s.N * e.H * e.W;
+  const size_t slab_b = (size_t)(h.splits > 1 ? h.splits : 0) * s.Cin * Ne * sizeof(float);
+  MD2_CHECK_ARG(ws.ptr && ws.bytes >= r.ws_bytes, "conv_dgrad: reflect workspace too small");
+  float* dxp = (float*)((char*)ws.ptr + slab_b);
+  ConvArgs ae = a;
+  fill_common(ae, e);
+  ae.Ho = s.Ho;
+  ae.Wo = s.Wo;
+  ae.HoWo = (long)s.Ho * s.Wo;
+  ae.HoWo4 = (uint32_t)(ae.HoWo * 4);
+  ae.g.N = Ne;
+  ae.fd_pix = make_fastdiv((uint32_t)(e.H * e.W));
+  ae.fd_row = make_fastdiv((uint32_t)e.W);
+  ae.hx_ext = 1;
+  TensorOut po{};
+  po.p0 = dxp;
+  po.c0 = s.Cin;
+  po.bs0 = (long)s.Cin * e.H * e.W;
+  ae.out = po;
+  MD2_CHECK_ARG((long)s.N * s.Cin * (s.H + 2) * (s.W + 2) < (1L << 31), "conv_dgrad: reflect fold index");
+  // split-K: the slabs [split][Cin][N][H+2][W+2] go straight to the fold (no reduce pass)
+  SplitKDefer df;
+  MD2_TRY(launch_px<1>(e, ae, r, r.tile, ws, st, &df));
+  const long HWp = (long)e.H * e.W;
+  const bool sl = df.slab != nullptr;
+  const long total = (long)s.N * s.Cin * s.H * s.W;
+  const bool small = s.H == 3 || s.W == 3;
+  // (four pixels per thread: W % 4 == 0, 16-byte aligned destination planes)
+  static const int f4on = tuning_knob("MD2_FOLD4", 1);
+  const bool f4 = f4on && !small && s.W % 4 == 0 && s.H >= 4 && s.W >= 8 && ((long)s.H * s.W) % 4 == 0 &&
+                  ((uintptr_t)dx.p0 % 16) == 0 && dx.bs0 % 4 == 0 &&
+                  (!dx.p1 || (((uintptr_t)dx.p1 % 16) == 0 && dx.bs1 % 4 == 0));
+  if (f4)
+    hipLaunchKernelGGL(fold_reflect4_kernel<0>, dim3(cdiv(total / 4, 256)), dim3(256), 0, st,
+                       sl ? df.slab : dxp, sl ? df.splits : 1, (long)s.Cin * Ne, sl ? HWp : s.Cin * HWp,
+                       sl ? Ne : HWp, dx, make_fastdiv((uint32_t)(s.H * s.W)),
+                       make_fastdiv((uint32_t)(s.W / 4)), make_fastdiv((uint32_t)s.Cin), s.H,
+                       (uint32_t)(total / 4));
+  else
+    hipLaunchKernelGGL(small ? fold_reflect_kernel<true> : fold_reflect_kernel<false>, dim3(cdiv(total, 256)),
+                       dim3(256), 0, st, sl ? df.slab : dxp, sl ? df.splits : 1, (long)s.Cin * Ne,
+                       sl ? HWp : s.Cin * HWp, sl ? Ne : HWp, dx, make_fastdiv((uint32_t)(s.H * s.W)),
+                       make_fastdiv((uint32_t)s.W), make_fastdiv((uint32_t)s.Cin), (uint32_t)total);
+  MD2_LAUNCH_CHECK();
+  return MD2_OK;
+}
+
+// PX_HALO_S2: the four output-parity classes from one staged dY image (conv_halo3s2_kernel): the
+// kernel iterates the dY grid; its split-K slabs [split][Cin][N H W] reduce as any dgrad's
+static int dgrad_halo_s2(const ConvShape& s, const PxRoute& r, const ConvArgs& a, ConvWorkspace ws,
+                         hipStream_t st) {
+  const HaloS2Plan& h2 = r.s2;
+  ConvArgs ak = a;
+  ak.g.N = (long)s.N * s.Ho * s.Wo;
+  ak.fd_pix = make_fastdiv((uint32_t)(s.Ho * s.Wo));
+  ak.fd_row = make_fastdiv((uint32_t)s.Wo);
+  ak.hx_cper = h2.cper;
+  ak.slab = nullptr;
+  if (h2.splits > 1) {
+    MD2_CHECK_ARG(ws.ptr && ws.bytes >= r.ws_bytes, "conv_dgrad: stride-2 halo workspace too small");
+    ak.slab = (float*)ws.ptr;
+  }
+  conv_arith_ref() = 6;
+  conv_note_kernel("halo_s2");
+  MD2_TRY(halo_s2_launch(ak, h2.items, h2.splits, st));
+  if (h2.splits > 1) {
+    ConvArgs ar = a;
+    ar.slab = ak.slab;
+    const TensorOut& o = a.out;
+    const bool aligned4 = a.fd_pix.d % 4 == 0 && o.bs0 % 4 == 0 && (!o.p1 || o.bs1 % 4 == 0) &&
+                          ((uintptr_t)o.p0 % 16) == 0 && (!o.p1 || ((uintptr_t)o.p1 % 16) == 0);
+    const long total = (long)a.g.M * a.g.N;
+    MD2_CHECK_ARG(total < (1L << 31), "conv_dgrad: split-K reduction index exceeds 2^31");
+    if (aligned4)
+      hipLaunchKernelGGL(splitk_reduce_px4_kernel<0>, dim3(cdiv(total / 4, 256)), dim3(256), 0, st, ar,
+                         h2.splits);
+    else
+      hipLaunchKernelGGL(splitk_reduce_px_kernel<0>, dim3(cdiv(total, 256)), dim3(256), 0, st, ar,
+                         h2.splits, 0, make_fastdiv((uint32_t)a.g.N), make_fastdiv((uint32_t)total));
+    MD2_LAUNCH_CHECK();
+  }
+  return MD2_OK;
+}
+
+// one output-parity class of the stride-2 dgrad as the GEMM extents of `ac`
+static void class_extents(ConvArgs& ac, const ConvShape& s, const PhaseClass& c) {
+  ac.g.N = (long)s.N * c.Hc * c.Wc;
+  ac.fd_pix = make_fastdiv((uint32_t)(c.Hc * c.Wc));
+  ac.fd_row = make_fastdiv((uint32_t)c.Wc);
+}
+
 int conv_dgrad(const ConvShape& s, const float* dy, const float* wpacked_d, const TensorOut& dx,
                ConvWorkspace ws, hipStream_t st, SplitKDefer* defer) {
   if (defer) *defer = SplitKDefer{};
   MD2_TRY(check_shape(s));
   MD2_CHECK_ARG(dy && wpacked_d && dx.p0, "conv_dgrad pointers");
   MD2_CHECK_ARG(!dx.bias && dx.act == ACT_NONE, "conv_dgrad: no bias/activation on dX");
-  if (head_path(s) && dx.c0 >= s.Cin) {
-    MD2_CHECK_ARG(!conv_px2_used(s, 1) && !conv_tap_major(s, 1), "head: packed layout");
-    conv_arith_ref() = 0;
-    HeadJob j = conv_head_job(s);
-    j.wd = conv_head_w(s, 1, wpacked_d);
-    j.dy = dy;
-    j.dx = dx.p0;
-    j.dxbs = dx.bs0;
-    if (s.reflect && !dx.accumulate && !heads_job_unfit(j)) {
-      conv_note_kernel("head_batched");
-      return heads_bwd(&j, 1, nullptr, 0, st);
-    }
-    conv_note_kernel("head_fallback");
-    return head_dgrad(j, s.reflect, dx.accumulate, st);
-  }
+  const PxRoute r = conv_dgrad_narrow(conv_route(s, 1), s, dx);
+  if (r.kind == PX_HEAD) return dgrad_head(s, r, dy, wpacked_d, dx, st);
   ConvArgs a{};
   fill_common(a, s);
   a.g.M = s.Cin;
   a.g.N = (long)s.N * s.H * s.W;
   a.g.K = s.Cout * s.KH * s.KW;
-  a.g.Mpad = (int)round_up(s.Cin, MPAD);
+  a.g.Mpad = r.Mpad;
   a.fd_pix = make_fastdiv((uint32_t)(s.H * s.W));
   a.fd_row = make_fastdiv((uint32_t)s.W);
   a.fd_bdiv = make_fastdiv(1u << 30);
   a.dy = dy;
   a.A = wpacked_d;
   a.out = dx;
-  a.A_bytes = (uint32_t)(conv_dgrad_packed_elems(s) * sizeof(float));
+  a.A_bytes = (uint32_t)(r.packed_elems * sizeof(float));
   MD2_CHECK_ARG((long)s.N * s.Cout * s.Ho * s.Wo * 4 < (long)OOB, "conv_dgrad: tensor exceeds 2 GB");
   a.b0_bytes = (uint32_t)((long)s.N * s.Cout * s.Ho * s.Wo * 4);
   a.b1_bytes = 0;
-  if (reflect_dgrad_on_halo(s)) {
-    // the full adjoint on the padded grid (split-K slabs first in the workspace, the padded
-    // image after them), then pad_reflect's adjoint into dX
-    const ConvShape e = reflect_ext_shape(s);
-    HaloPlan h;
-    reflect_dgrad_on_halo(s, &h);
-    const long Ne = (long)s.N * e.H * e.W;
-    const size_t slab_b = (size_t)(h.splits > 1 ? h.splits : 0) * s.Cin * Ne * sizeof(float);
-    MD2_CHECK_ARG(ws.ptr && ws.bytes >= slab_b + (size_t)s.Cin * Ne * sizeof(float),
-                  "conv_dgrad: reflect workspace too small");
-    float* dxp = (float*)((char*)ws.ptr + slab_b);
-    ConvArgs ae = a;
-    fill_common(ae, e);
-    ae.Ho = s.Ho;
-    ae.Wo = s.Wo;
-    ae.HoWo = (long)s.Ho * s.Wo;
-    ae.HoWo4 = (uint32_t)(ae.HoWo * 4);
-    ae.g.N = Ne;
-    ae.fd_pix = make_fastdiv((uint32_t)(e.H * e.W));
-    ae.fd_row = make_fastdiv((uint32_t)e.W);
-    ae.hx_ext = 1;
-    TensorOut po{};
-    po.p0 = dxp;
-    po.c0 = s.Cin;
-    po.bs0 = (long)s.Cin * e.H * e.W;
-    ae.out = po;
-    MD2_CHECK_ARG((long)s.N * s.Cin * (s.H + 2) * (s.W + 2) < (1L << 31), "conv_dgrad: reflect fold index");
-    const Plan p = plan_px(ae.g.M, ae.g.N, ae.g.K, s.Cout % 32 == 0);
-    // split-K: the slabs [split][Cin][N][H+2][W+2] go straight to the fold (no reduce pass)
-    SplitKDefer df;
-    MD2_TRY(launch_px<1>(e, ae, p, ConvWorkspace{ws.ptr, slab_b}, st, &df));
-    const long HWp = (long)e.H * e.W;
-    const bool sl = df.slab != nullptr;
-    const long total = (long)s.N * s.Cin * s.H * s.W;
-    const bool small = s.H == 3 || s.W == 3;
-    // (four pixels per thread: W % 4 == 0, 16-byte aligned destination planes)
-    static const int f4on = tuning_knob("MD2_FOLD4", 1);
-    const bool f4 = f4on && !small && s.W % 4 == 0 && s.H >= 4 && s.W >= 8 && ((long)s.H * s.W) % 4 == 0 &&
-                    ((uintptr_t)dx.p0 % 16) == 0 && dx.bs0 % 4 == 0 &&
-                    (!dx.p1 || (((uintptr_t)dx.p1 % 16) == 0 && dx.bs1 % 4 == 0));
-    if (f4)
-      hipLaunchKernelGGL(fold_reflect4_kernel<0>, dim3(cdiv(total / 4, 256)), dim3(256), 0, st,
-                         sl ? df.slab : dxp, sl ? df.splits : 1, (long)s.Cin * Ne, sl ? HWp : s.Cin * HWp,
-                         sl ? Ne : HWp, dx, make_fastdiv((uint32_t)(s.H * s.W)),
-                         make_fastdiv((uint32_t)(s.W / 4)), make_fastdiv((uint32_t)s.Cin), s.H,
-                         (uint32_t)(total / 4));
-    else
-      hipLaunchKernelGGL(small ? fold_reflect_kernel<true> : fold_reflect_kernel<false>, dim3(cdiv(total, 256)),
-                         dim3(256), 0, st, sl ? df.slab : dxp, sl ? df.splits : 1, (long)s.Cin * Ne,
-                         sl ? HWp : s.Cin * HWp, sl ? Ne : HWp, dx, make_fastdiv((uint32_t)(s.H * s.W)),
-                         make_fastdiv((uint32_t)s.W), make_fastdiv((uint32_t)s.Cin), (uint32_t)total);
-    MD2_LAUNCH_CHECK();
-    return MD2_OK;
-  }
-  if (const HaloS2Plan h2 = plan_halo_s2(s); h2.ok) {
-    // the four output-parity classes from one staged dY image (conv_halo3s2_kernel): the kernel
-    // iterates the dY grid; its split-K slabs [split][Cin][N H W] reduce as any dgrad's
-    ConvArgs ak = a;
-    ak.g.N = (long)s.N * s.Ho * s.Wo;
-    ak.fd_pix = make_fastdiv((uint32_t)(s.Ho * s.Wo));
-    ak.fd_row = make_fastdiv((uint32_t)s.Wo);
-    ak.hx_cper = h2.cper;
-    ak.slab = nullptr;
-    if (h2.splits > 1) {
-      const size_t need = (size_t)h2.splits * a.g.M * a.g.N * sizeof(float);
-      MD2_CHECK_ARG(ws.ptr && ws.bytes >= need, "conv_dgrad: stride-2 halo workspace too small");
-      ak.slab = (float*)ws.ptr;
-    }
-    conv_arith_ref() = 6;
-    conv_note_kernel("halo_s2");
-    MD2_TRY(halo_s2_launch(ak, h2.items, h2.splits, st));
-    if (h2.splits > 1) {
-      ConvArgs ar = a;
-      ar.slab = ak.slab;
-      const TensorOut& o = a.out;
-      const bool aligned4 = a.fd_pix.d % 4 == 0 && o.bs0 % 4 == 0 && (!o.p1 || o.bs1 % 4 == 0) &&
-                            ((uintptr_t)o.p0 % 16) == 0 && (!o.p1 || ((uintptr_t)o.p1 % 16) == 0);
-      const long total = (long)a.g.M * a.g.N;
-      MD2_CHECK_ARG(total < (1L << 31), "conv_dgrad: split-K reduction index exceeds 2^31");
-      if (aligned4)
-        hipLaunchKernelGGL(splitk_reduce_px4_kernel<0>, dim3(cdiv(total / 4, 256)), dim3(256), 0, st, ar,
-                           h2.splits);
-      else
-        hipLaunchKernelGGL(splitk_reduce_px_kernel<0>, dim3(cdiv(total, 256)), dim3(256), 0, st, ar,
-                           h2.splits, 0, make_fastdiv((uint32_t)a.g.N), make_fastdiv((uint32_t)total));
-      MD2_LAUNCH_CHECK();
-    }
-    return MD2_OK;
-  }
-  if (s.stride == 2 && conv_tap_major(s, 1) && conv_px2_used(s, 1) && s.KH <= 3 && s.H % 2 == 0 &&
-      s.W % 2 == 0) {
-    // the four output-parity classes (each a dense GEMM over only its own taps) in ONE launch:
-    // equal extents, K of the largest class; smaller classes' surplus splits write zero slabs
-    ConvArgs ac = a;
-    int kmax = 0;
-    for (int cls = 0; cls < 4; ++cls) {
-      const PhaseClass c = phase_class(s, cls >> 1, cls & 1);
-      ac.ph_y0c[cls] = c.y0;
-      ac.ph_x0c[cls] = c.x0;
-      ac.ph_ntc[cls] = c.ntaps;
-      for (int t = 0; t < 4; ++t) ac.ph_taps[4 * cls + t] = t < c.ntaps ? c.taps[t] : 0;
-      kmax = std::max(kmax, c.ntaps);
-      if (cls == 0) {
-        ac.g.N = (long)s.N * c.Hc * c.Wc;
-        ac.fd_pix = make_fastdiv((uint32_t)(c.Hc * c.Wc));
-        ac.fd_row = make_fastdiv((uint32_t)c.Wc);
-      }
-    }
-    ac.g.K = kmax * s.Cout;
-    ac.ph_S = 1;
-    const Plan p = plan_px(ac.g.M, 4 * ac.g.N, ac.g.K, s.Cout % 32 == 0, true);
-    return launch_px<1>(s, ac, p, ws, st);
-  }
-  if (s.stride == 2 && conv_tap_major(s, 1)) {
-    // four dense GEMMs over the output-parity classes, each with only its own taps
-    for (int cls = 0; cls < 4; ++cls) {
-      const PhaseClass c = phase_class(s, cls >> 1, cls & 1);
-      if (c.Hc <= 0 || c.Wc <= 0 || (c.ntaps == 0 && dx.accumulate)) continue;
+  switch (r.kind) {
+    case PX_REFLECT_HALO: return dgrad_reflect_halo(s, r, a, dx, ws, st);
+    case PX_HALO_S2: return dgrad_halo_s2(s, r, a, ws, st);
+    case PX_CLASSES_MERGED: {
+      // ONE launch: equal extents, K of the largest class; smaller classes' surplus splits write
+      // zero slabs
       ConvArgs ac = a;
-      ac.ph_y0 = c.y0;
-      ac.ph_x0 = c.x0;
-      for (int t = 0; t < 16; ++t) ac.ph_taps[t] = t < c.ntaps ? c.taps[t] : 0;
-      ac.g.N = (long)s.N * c.Hc * c.Wc;
-      ac.g.K = c.ntaps * s.Cout;
-      ac.fd_pix = make_fastdiv((uint32_t)(c.Hc * c.Wc));
-      ac.fd_row = make_fastdiv((uint32_t)c.Wc);
-      const Plan p = plan_px(ac.g.M, ac.g.N, ac.g.K, s.Cout % 32 == 0);
-      MD2_TRY(launch_px<1>(s, ac, p, ws, st));
+      int kmax = 0;
+      for (int cls = 0; cls < 4; ++cls) {
+        const PhaseClass& c = r.cls[cls];
+        ac.ph_y0c[cls] = c.y0;
+        ac.ph_x0c[cls] = c.x0;
+        ac.ph_ntc[cls] = c.ntaps;
+        for (int t = 0; t < 4; ++t) ac.ph_taps[4 * cls + t] = t < c.ntaps ? c.taps[t] : 0;
+        kmax = std::max(kmax, c.ntaps);
+      }
+      class_extents(ac, s, r.cls[0]);
+      ac.g.K = kmax * s.Cout;
+      ac.ph_S = 1;
+      return launch_px<1>(s, ac, r, r.cls_plan[0], ws, st);
     }
-    return MD2_OK;
+    case PX_CLASSES4:
+      for (int cls = 0; cls < 4; ++cls) {
+        const PhaseClass& c = r.cls[cls];
+        if (c.Hc <= 0 || c.Wc <= 0 || (c.ntaps == 0 && dx.accumulate)) continue;
+        ConvArgs ac = a;
+        ac.ph_y0 = c.y0;
+        ac.ph_x0 = c.x0;
+        for (int t = 0; t < 16; ++t) ac.ph_taps[t] = t < c.ntaps ? c.taps[t] : 0;
+        class_extents(ac, s, c);
+        ac.g.K = c.ntaps * s.Cout;
+        MD2_TRY(launch_px<1>(s, ac, r, r.cls_plan[cls], ws, st));
+      }
+      return MD2_OK;
+    case PX_PX16:
+    case PX_HALO:
+    case PX_HALO2D:
+    case PX_TILE:
+      return launch_px<1>(s, a, r, r.tile, ws, st, defer);
+    default:
+      set_error("conv_dgrad: not a data-gradient route");
+      return MD2_EINVAL;
   }
-  const Plan p = plan_px(a.g.M, a.g.N, a.g.K, conv_tap_major(s, 1) && s.Cout % 32 == 0);
-  return launch_px<1>(s, a, p, ws, st, defer);
 }
 
 }  // namespace md2

@@ -1020,7 +1020,7 @@ __global__ __launch_bounds__(384, 3) void conv_whalo_kernel(ConvArgs a) {   // 3
   }
 }
 
-// launch (conv.hip plan_halo chose the shape): grid (N / 256, M / 64, splits), 512 threads,
+// launch (conv_route.hip plan_halo chose the shape): grid (N / 256, M / 64, splits), 512 threads,
 // the two LDS image buffers as dynamic shared memory
 template <int MODE, int RFL, int EXT>
 static int halo_launch_as(const ConvArgs& a, int items, int splits, hipStream_t st) {
@@ -1065,7 +1065,7 @@ int halo_s2_launch(const ConvArgs& a, int items, int splits, hipStream_t st) {
   return lds_launch<conv_halo3s2_kernel<1>>(grid, dim3(512), z, st, a);
 }
 
-// 2D-tile halo kernel (conv.hip plan_halo, h.d2): grid (images x tiles, M / (32 MW), splits)
+// 2D-tile halo kernel (conv_route.hip plan_halo, h.d2): grid (images x tiles, M / (32 MW), splits)
 template <int MODE, int RFL, int EXT>
 static int halo2d_launch_as(const ConvArgs& a, int mw, int splits, hipStream_t st) {
   const long tiles = (long)cdiv(a.W, H2_TW) * cdiv(a.H, H2_TH);

@@ -1,9 +1,12 @@
-// Implicit-GEMM convolution kernels for gfx950 (see conv.h).  This header: what all six conv units
+// Implicit-GEMM convolution kernels for gfx950 (see conv.h).  This header: what all seven conv units
 // share (device helpers, kernel arguments, the dynamic-LDS launch).  conv_plan.h: host-only plan
-// structs and declarations; the planners are defined once, in conv.hip (with packing, predicates,
-// workspace sizing, act_backward).  conv_px_launch.h: the fwd / dgrad kernels (conv_px*.inc) and
-// launchers of conv_fwd.hip and conv_dgrad.hip.  conv_wgrad.hip: conv_wgrad_kernels.inc,
-// conv_wpx3.inc, launchers, conv_wgrad.  conv_halo.hip / conv_stem.hip: conv_halo.inc / conv_stem.inc.
+// structs, the route of a pass (PxRoute / WRoute) and declarations.  conv_route.hip (no kernels):
+// the planners, the selection predicates, conv_route / conv_wgrad_route and their narrowing by
+// the operands of a call, workspace and packed sizes -- the one place a kernel is chosen.
+// conv.hip: the pack kernels, the kernel-note helpers, act_backward.  conv_px_launch.h: the fwd /
+// dgrad kernels (conv_px*.inc) and launchers of conv_fwd.hip and conv_dgrad.hip, which switch on
+// the route's kind.  conv_wgrad.hip: conv_wgrad_kernels.inc, conv_wpx3.inc, launchers, conv_wgrad.
+// conv_halo.hip / conv_stem.hip: conv_halo.inc / conv_stem.inc.
 // conv_api.hip: the C entry points that carry the executor's operand forms (md2_conv2d_*_ex; no kernels).
 //
 // All three passes are one GEMM shape  C[M][N] = sum_k A[k][m] * B[k][n]  computed with the

@@ -1,6 +1,6 @@
 // Dynamic-LDS geometry of the six conv kernels that size their shared memory at launch
 // (conv_halo.inc, conv_stem.inc) -- stated ONCE: the kernels take their plane sizes and offsets
-// from here, the planners (conv.hip plan_halo / plan_halo_s2 / plan_whalo, conv_stem.inc
+// from here, the planners (conv_route.hip plan_halo / plan_halo_s2 / plan_whalo,
 // stem_*_applies) admit a shape with fits(), and the launchers allocate bytes() under the opt-in
 // ceiling cap through lds_launch (conv_kernel.h), which refuses a launch with need() > bytes().
 // A launcher that allocated another kernel's size used to compute garbage without a fault.

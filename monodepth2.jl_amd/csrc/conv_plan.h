@@ -1,5 +1,5 @@
-// Host side of the conv passes: tile tables, plan structs, the planners and selection glue (defined
-// once, in conv.hip: sizing and launching read the same plan) and the cross-unit launchers.
+// Host side of the conv passes: tile tables, plan structs, the route of a pass (defined once, in
+// conv_route.hip: packing, sizing and launching read the same decision) and the cross-unit launchers.
 #pragma once
 #include "conv_kernel.h"
 #include "head.h"
@@ -54,21 +54,49 @@ struct PhaseClass {
   int taps[16];
 };
 
-Plan plan_px(int M, long N, int K, bool bk32_ok = false, bool prefer32 = false);
-HaloPlan plan_halo(const ConvShape& s, int mode);
-HaloS2Plan plan_halo_s2(const ConvShape& s);
-WHaloPlan plan_whalo(const ConvShape& s, int c0);
-WPlan plan_wgrad(const ConvShape& s, int c0);
-int wgrad_cw(const ConvShape& s, int c0, int BN);
-ConvShape reflect_ext_shape(const ConvShape& s);
-bool reflect_dgrad_on_halo(const ConvShape& s, HaloPlan* hp = nullptr);
-size_t reflect_dgrad_ws(const ConvShape& s);
-PhaseClass phase_class(const ConvShape& s, int cy, int cx);
+// ---- the route of a pass: which kernel runs it, decided once (conv_route.hip).  Packing, the
+// workspace sizes and the launchers all read this; none of them tests a shape again.
+enum PxKind { PX_HEAD, PX_STEM_S2D, PX_PX16, PX_HALO, PX_HALO2D, PX_REFLECT_HALO, PX_HALO_S2,
+              PX_CLASSES_MERGED, PX_CLASSES4, PX_TILE };
+enum PxArith { ARITH_PX, ARITH_PX2, ARITH_PX3 };   // the tile kernel: conv_px / conv_px2 / conv_px3
+struct PxRoute {
+  PxKind kind;
+  PxArith arith;
+  // the packed operand: layout 0 [Kpad][Mpad] fp32, 1 [Kpad/16][Mpad][16] fp32, 2 [Kpad/16][3][Mpad][16]
+  // bf16 split terms; tap: tap-major K order
+  int layout, tap, Kpad, Mpad;
+  size_t packed_elems;
+  Plan tile;           // always filled: the tile kinds' plan, and the fallback of a vetoed kind
+  HaloPlan halo;       // PX_HALO, PX_HALO2D; PX_REFLECT_HALO: the plan of `ext`
+  ConvShape ext;       // PX_REFLECT_HALO: the zero-padded dgrad on the (H+2) x (W+2) grid
+  HaloS2Plan s2;       // PX_HALO_S2
+  PhaseClass cls[4];   // the stride-2 dgrad's output-parity classes
+  Plan cls_plan[4];    // PX_CLASSES4: one per class; PX_CLASSES_MERGED: [0], the one launch
+  size_t ws_bytes;     // workspace of the kind and of what it can narrow to
+};
+// forward (mode 0) / data gradient (mode 1): a pure function of the shape and the tuning knobs
+PxRoute conv_route(const ConvShape& s, int mode);
+// the route that runs with the operands of one call (every operand condition is stated here)
+PxRoute conv_fwd_narrow(PxRoute r, const ConvShape& s, const TensorIn& x, const TensorOut& y);
+PxRoute conv_dgrad_narrow(PxRoute r, const ConvShape& s, const TensorOut& dx);
+
+enum WKind { W_HEAD, W_WHALO, W_STEM_S2D, W_STEM, W_WGRAD16, W_TILE };
+struct WRoute {
+  WKind kind;
+  WKind base;        // what a vetoed W_WHALO / W_STEM_S2D narrows to (from tile.tile)
+  WPlan tile;
+  WHaloPlan halo;
+  int nsplit;        // slabs of `kind`; the bias partials sit behind them
+  size_t ws_bytes;
+};
+// c0: channels of the first input tensor (>= Cin: one tensor)
+WRoute conv_wgrad_route(const ConvShape& s, int c0);
+WRoute conv_wgrad_narrow(WRoute r, const ConvShape& s, const TensorIn& x);
+
 void fill_common(ConvArgs& a, const ConvShape& s);
 int check_shape(const ConvShape& s);
-int px3_terms();
+int px3_terms();     // 6 or 9 products (MD2_PX3_TERMS, read here only)
 int bias_parts(int C, long total);
-bool head_path(const ConvShape& s);
 
 // the LDS-halo kernels (conv_halo.inc, its own translation unit conv_halo.hip)
 int halo_launch(int mode, const ConvArgs& a, int items, int splits, int reflect, hipStream_t st);
@@ -76,9 +104,7 @@ int halo2d_launch(int mode, const ConvArgs& a, int mw, int splits, int reflect, 
 int halo_s2_launch(const ConvArgs& a, int items, int splits, hipStream_t st);
 int whalo_launch(const ConvArgs& a, int items, int ksteps, int splits, hipStream_t st);
 // the ResNet stem forward on the space-to-depth grid (conv_stem.inc, translation unit conv_stem.hip)
-bool stem_s2d_applies(const ConvShape& s, const TensorIn& x, const TensorOut& y);
 int stem_s2d_launch(const ConvShape& s, const ConvArgs& a, hipStream_t st);
-bool stem_wgrad_s2d_applies(const ConvShape& s, const TensorIn& x);
 int stem_wgrad_blocks(const ConvShape& s);
 int stem_wgrad_s2d_launch(const ConvShape& s, const ConvArgs& a, hipStream_t st);
 

@@ -84,9 +84,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_px_kernel(ConvArgs a, int s
 }
 
 template <int MODE, int BM, int BN, int WM, int WN>
-int launch_px_tile(const ConvShape& s, const ConvArgs& a, bool tap, int bk, dim3 grid, hipStream_t st) {
-  const bool v2 = conv_px2_used(s, MODE);
-  const bool v3 = conv_px3_used(s, MODE);
+int launch_px_tile(const ConvShape& s, const ConvArgs& a, PxArith arith, bool tap, int bk, dim3 grid,
+                   hipStream_t st) {
+  const bool v2 = arith == ARITH_PX2, v3 = arith == ARITH_PX3;
 #define MD2_PX_CASE(KS, SS, RR)                                                                  \
   if (s.KH == KS && s.stride == SS && s.reflect == RR) {                                         \
     if constexpr (BM >= 32 && BN % 64 == 0 && WM * WN == 4) {                                    \
@@ -169,39 +169,34 @@ int launch_px16(const ConvShape& s, ConvArgs& a, hipStream_t st) {
   return MD2_ENOTSUP;
 }
 
+// the kernel the route names: the 16-row kernel, an LDS-halo kernel (r.halo) or the tile `tile`
+// (r.tile, or a parity class's own), then the split-K reduction unless the caller takes the slabs
 template <int MODE>
-int launch_px(const ConvShape& s, ConvArgs& a, const Plan& p_in, ConvWorkspace ws, hipStream_t st,
-              SplitKDefer* defer = nullptr) {
+int launch_px(const ConvShape& s, ConvArgs& a, const PxRoute& r, const Plan& tile, ConvWorkspace ws,
+              hipStream_t st, SplitKDefer* defer = nullptr) {
   double* const stats = defer ? defer->stats : nullptr;
   const bool keep_reduce = defer && defer->keep_reduce;
   if (defer) *defer = SplitKDefer{};
-  if (conv_px16_used(s, MODE)) return launch_px16<MODE>(s, a, st);
-  // the LDS-halo kernel where it applies (plain input: one tensor, no frame-strided images)
-  HaloPlan hp = plan_halo(s, MODE);
-  // (forward input: no frame-strided images; a concat split on a 16-channel chunk boundary)
-  if (hp.ok && MODE == 0 && (a.in.bdiv < s.N || (a.in.p1 && a.in.c0 < s.Cin && a.in.c0 % 16))) hp.ok = false;
-  Plan p = p_in;
-  if (hp.ok) {
+  if (r.kind == PX_PX16) return launch_px16<MODE>(s, a, st);
+  const bool halo = r.kind == PX_HALO || r.kind == PX_HALO2D || r.kind == PX_REFLECT_HALO;
+  const HaloPlan& hp = r.halo;
+  Plan p = tile;
+  if (halo) {
     p.splits = hp.splits;
     p.kper = hp.cper * 16;   // only the slab count matters below
   }
   a.g.kper = p.kper;
   a.slab = nullptr;
   if (p.splits > 1) {
-    const size_t need = (size_t)p.splits * a.g.M * a.g.N * sizeof(float);
-    MD2_CHECK_ARG(ws.ptr && ws.bytes >= need, "conv split-K workspace too small");
+    MD2_CHECK_ARG(ws.ptr && ws.bytes >= r.ws_bytes, "conv split-K workspace too small");
     a.slab = (float*)ws.ptr;
   }
   const int ncls = (MODE == 1 && a.ph_S > 0) ? 4 : 1;   // merged stride-2 dgrad classes
-  if (ncls > 1) {
-    a.ph_S = p.splits;
-    MD2_CHECK_ARG(p.splits == 1 || (ws.ptr && ws.bytes >= 4 * (size_t)p.splits * a.g.M * a.g.N * sizeof(float)),
-                  "conv split-K workspace too small");
-  }
+  if (ncls > 1) a.ph_S = p.splits;
   dim3 grid(cdiv(a.g.N, p.BN), cdiv(a.g.M, p.BM), p.splits * ncls);
-  const bool tap = conv_tap_major(s, MODE);
+  const bool tap = r.tap;
   int rc;
-  if (hp.ok && ncls == 1) {
+  if (halo) {
     a.hx_cper = hp.cper;
     // BN statistics in the epilogue: forward, no split-K, a plain contiguous output
     const TensorOut& oo = a.out;
@@ -218,14 +213,14 @@ int launch_px(const ConvShape& s, ConvArgs& a, const Plan& p_in, ConvWorkspace w
       defer->stats_parts = (int)cdiv(a.g.N, 256);
     }
   } else switch (p.tile) {
-    case T128x128: rc = launch_px_tile<MODE, 128, 128, 2, 2>(s, a, tap, p.BK, grid, st); break;
-    case T64x256: rc = launch_px_tile<MODE, 64, 256, 1, 4>(s, a, tap, p.BK, grid, st); break;
-    case T64x128: rc = launch_px_tile<MODE, 64, 128, 2, 2>(s, a, tap, p.BK, grid, st); break;
-    case T128x64: rc = launch_px_tile<MODE, 128, 64, 2, 2>(s, a, tap, p.BK, grid, st); break;
-    case T64x64: rc = launch_px_tile<MODE, 64, 64, 2, 2>(s, a, tap, p.BK, grid, st); break;
-    case T32x128: rc = launch_px_tile<MODE, 32, 128, 1, 4>(s, a, tap, p.BK, grid, st); break;
-    case T128x64q: rc = launch_px_tile<MODE, 128, 64, 4, 1>(s, a, tap, p.BK, grid, st); break;
-    default: rc = launch_px_tile<MODE, 32, 256, 1, 4>(s, a, tap, p.BK, grid, st); break;
+    case T128x128: rc = launch_px_tile<MODE, 128, 128, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
+    case T64x256: rc = launch_px_tile<MODE, 64, 256, 1, 4>(s, a, r.arith, tap, p.BK, grid, st); break;
+    case T64x128: rc = launch_px_tile<MODE, 64, 128, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
+    case T128x64: rc = launch_px_tile<MODE, 128, 64, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
+    case T64x64: rc = launch_px_tile<MODE, 64, 64, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
+    case T32x128: rc = launch_px_tile<MODE, 32, 128, 1, 4>(s, a, r.arith, tap, p.BK, grid, st); break;
+    case T128x64q: rc = launch_px_tile<MODE, 128, 64, 4, 1>(s, a, r.arith, tap, p.BK, grid, st); break;
+    default: rc = launch_px_tile<MODE, 32, 256, 1, 4>(s, a, r.arith, tap, p.BK, grid, st); break;
   }
   if (rc) return rc;
   const TensorOut& o = a.out;
@@ -235,7 +230,7 @@ int launch_px(const ConvShape& s, ConvArgs& a, const Plan& p_in, ConvWorkspace w
     defer->splits = p.splits;
     return MD2_OK;
   }
-  const int phase = (int)(MODE == 1 && s.stride == 2 && conv_tap_major(s, 1));
+  const int phase = (int)(MODE == 1 && s.stride == 2 && tap);
   const bool aligned4 = a.fd_pix.d % 4 == 0 && o.bs0 % 4 == 0 && (!o.p1 || o.bs1 % 4 == 0) &&
                         ((uintptr_t)o.p0 % 16) == 0 && (!o.p1 || ((uintptr_t)o.p1 % 16) == 0);
   if (p.splits > 1 && ncls == 1 && !phase && aligned4) {
@@ -249,8 +244,7 @@ int launch_px(const ConvShape& s, ConvArgs& a, const Plan& p_in, ConvWorkspace w
     const long total = (long)a.g.M * a.g.N * ncls;
     MD2_CHECK_ARG(total < (1L << 31), "conv: split-K reduction index exceeds 2^31");
     hipLaunchKernelGGL(splitk_reduce_px_kernel<0>, dim3(cdiv(total, 256)), dim3(256), 0, st, a, p.splits,
-                       (int)(MODE == 1 && s.stride == 2 && conv_tap_major(s, 1)),
-                       make_fastdiv((uint32_t)a.g.N), make_fastdiv((uint32_t)((long)a.g.M * a.g.N)));
+                       phase, make_fastdiv((uint32_t)a.g.N), make_fastdiv((uint32_t)((long)a.g.M * a.g.N)));
     MD2_LAUNCH_CHECK();
   }
   return MD2_OK;

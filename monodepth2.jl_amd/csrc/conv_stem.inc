@@ -507,28 +507,10 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_stem_s2d_kernel(ConvArgs a,
   }
 }
 
-bool stem_s2d_applies(const ConvShape& s, const TensorIn& x, const TensorOut& y) {
-  static const int on = tuning_knob("MD2_STEM_S2D", 1);
-  if (!on || s.KH != 7 || s.KW != 7 || s.stride != 2 || s.pad != 3 || s.reflect || s.Cin != 3 || s.Cout != 64) return false;
-  if (s.cin_w && s.cin_w != 3) return false;
-  if (s.H % 2 || s.W % 2 || s.Wo % 16 || s.Ho != s.H / 2 || s.Wo != s.W / 2) return false;
-  if (!StemLds::fits(s.Wo)) return false;                // the LDS ring (Wo <= 338: <= 21 subtiles per row)
-  if (x.p1 || x.c0 < s.Cin) return false;
-  if (y.bias || y.act != ACT_NONE || y.accumulate || y.c0 < s.Cout) return false;
-  return (long)s.N * s.Ho * s.Wo < (1L << 31);
-}
-
+// (which shapes and operands run these kernels: conv_route.hip)
 // blocks: one per CU (256), at most one per output row
 static int stem_blocks(const ConvShape& s) { return (int)std::min<long>(256, (long)s.N * s.Ho); }
 
-// the filter-gradient kernel: the forward's conditions on the input and its own ring
-// (StemWgradLds: the pitch P, the combine buffer over the ring)
-bool stem_wgrad_s2d_applies(const ConvShape& s, const TensorIn& x) {
-  static const int on = tuning_knob("MD2_WSTEM_S2D", 1);
-  TensorOut y;
-  if (!on || !stem_s2d_applies(s, x, y)) return false;
-  return StemWgradLds::fits(s.Wo) && (long)s.N * s.Cout * s.Ho * s.Wo * 4 < (long)OOB;
-}
 int stem_wgrad_blocks(const ConvShape& s) { return stem_blocks(s); }
 int stem_wgrad_s2d_launch(const ConvShape& s, const ConvArgs& a, hipStream_t st) {
   const int P = StemWgradLds::pitch(s.Wo);

@@ -81,27 +81,57 @@ int launch_w(int cw, const ConvArgs& a, dim3 grid, hipStream_t st) {
   return MD2_OK;
 }
 
+// W_HEAD: the batched kernel where this call's alignment and store mode fit it
+static int wgrad_head(const ConvShape& s, const TensorIn& x, const float* dy, float* dw, float* db,
+                      int accumulate, ConvWorkspace ws, hipStream_t st) {
+  conv_arith_ref() = 0;
+  HeadJob j = conv_head_job(s);
+  j.x = conv_head_in(x);
+  j.dy = dy;
+  j.dw = dw;
+  j.db = db;
+  if (s.reflect && !accumulate && !heads_job_unfit(j)) {
+    conv_note_kernel("head_batched");
+    return heads_bwd(&j, 1, ws.ptr, ws.bytes, st);
+  }
+  conv_note_kernel("head_fallback");
+  return head_wgrad(j, s.reflect, accumulate, ws.ptr, ws.bytes, st);
+}
+
+// W_TILE: the generic tiles of the plan
+static int launch_w_tile(const ConvShape& s, const WPlan& p, const ConvArgs& a, dim3 grid, hipStream_t st) {
+#define MD2_W_CASE(KS, SS, RR)                                                                     \
+  if (s.KH == KS && s.stride == SS && s.reflect == RR) {                                           \
+    switch (p.tile) {                                                                              \
+      case W32x256: return launch_w<32, 256, 1, 4, KS, SS, RR>(p.cw, a, grid, st);                 \
+      case W64x64: return launch_w<64, 64, 2, 2, KS, SS, RR>(p.cw, a, grid, st);                   \
+      case W32x128: return launch_w<32, 128, 1, 4, KS, SS, RR>(p.cw, a, grid, st);                 \
+      case W64x192:                                                                                \
+        if constexpr (KS == 3) {                                                                   \
+          if (p.cw == 64) {                                                                        \
+            launch_w_cw<64, 192, 2, 2, KS, SS, RR, 64>(a, grid, st);                               \
+            return MD2_OK;                                                                         \
+          }                                                                                        \
+        }                                                                                          \
+        return MD2_ENOTSUP;                                                                        \
+      default: return launch_w<64, 128, 2, 2, KS, SS, RR>(p.cw, a, grid, st);                      \
+    }                                                                                              \
+  }
+  MD2_CONV_COMBOS(MD2_W_CASE)
+#undef MD2_W_CASE
+  return MD2_ENOTSUP;
+}
+
 int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw, float* db,
                int accumulate, ConvWorkspace ws, hipStream_t st, const float* db_part,
                int db_parts) {
   MD2_TRY(check_shape(s));
   MD2_CHECK_ARG(x.p0 && dy && dw, "conv_wgrad pointers");
   MD2_CHECK_ARG(x.c0 >= s.Cin || x.p1 != nullptr, "conv_wgrad: second input tensor missing");
-  if (head_path(s) && x.c0 >= s.Cin) {
-    conv_arith_ref() = 0;
-    HeadJob j = conv_head_job(s);
-    j.x = conv_head_in(x);
-    j.dy = dy;
-    j.dw = dw;
-    j.db = db;
-    if (s.reflect && !accumulate && !heads_job_unfit(j)) {
-      conv_note_kernel("head_batched");
-      return heads_bwd(&j, 1, ws.ptr, ws.bytes, st);
-    }
-    conv_note_kernel("head_fallback");
-    return head_wgrad(j, s.reflect, accumulate, ws.ptr, ws.bytes, st);
-  }
-  const WPlan p = plan_wgrad(s, x.c0);
+  const WRoute rt = conv_wgrad_narrow(conv_wgrad_route(s, x.c0), s, x);
+  if (rt.kind == W_HEAD) return wgrad_head(s, x, dy, dw, db, accumulate, ws, st);
+  const WPlan& p = rt.tile;
+  const WHaloPlan& hx = rt.halo;
   const bool tap = p.cw > 0;
   ConvArgs a{};
   fill_common(a, s);
@@ -128,88 +158,66 @@ int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw
     a.A_bytes = (uint32_t)(extd * 4);
   }
   a.g.kper = p.kper;
-  const size_t need = conv_wgrad_workspace(s);
-  MD2_CHECK_ARG(ws.ptr && ws.bytes >= need, "conv_wgrad workspace too small");
+  MD2_CHECK_ARG(ws.ptr && ws.bytes >= rt.ws_bytes, "conv_wgrad workspace too small");
   a.slab = (float*)ws.ptr;
   const long total = (long)a.g.M * a.g.N;
-  const WHaloPlan hx = x.bdiv >= s.N ? plan_whalo(s, x.c0) : WHaloPlan{};
-  // the stem on the space-to-depth kernel (conv_stem.inc): one slab per block
-  const bool stem2 = !hx.ok && p.tile == WSTEM && stem_wgrad_s2d_applies(s, x);
-  const int nsplit = hx.ok ? hx.splits : stem2 ? stem_wgrad_blocks(s) : p.splits;
+  const int nsplit = rt.nsplit;
   float* bpart = a.slab + (long)nsplit * total;
   dim3 grid((unsigned)p.ntiles_n, cdiv(a.g.M, p.BM), p.splits);
   int rc = MD2_ENOTSUP;
-  if (hx.ok) {
-    a.hx_r = hx.r;
-    a.hx_nchunk = hx.nchunk;
-    a.hx_cper = hx.cper;
-    conv_arith_ref() = 6;
-    conv_note_kernel("whalo");
-    rc = whalo_launch(a, hx.items, cdiv(hx.r * s.W, 16), hx.splits, st);
-    if (rc) return rc;
-  }
-  if (stem2) {
-    conv_arith_ref() = 6;
-    conv_note_kernel("stem_wgrad_s2d");
-    rc = stem_wgrad_s2d_launch(s, a, st);
-  }
-  if (rc == MD2_ENOTSUP && p.tile == WSTEM) {
-    conv_arith_ref() = 1;
-    conv_note_kernel("stem_wgrad");
-    const dim3 gs((unsigned)p.splits);
-    switch (s.Cin) {
-      case 1: hipLaunchKernelGGL(conv_wgrad_stem_kernel<1>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
-      case 2: hipLaunchKernelGGL(conv_wgrad_stem_kernel<2>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
-      case 3: hipLaunchKernelGGL(conv_wgrad_stem_kernel<3>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
-      case 4: hipLaunchKernelGGL(conv_wgrad_stem_kernel<4>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
-      default: break;
+  switch (rt.kind) {
+    case W_WHALO:
+      a.hx_r = hx.r;
+      a.hx_nchunk = hx.nchunk;
+      a.hx_cper = hx.cper;
+      conv_arith_ref() = 6;
+      conv_note_kernel("whalo");
+      rc = whalo_launch(a, hx.items, cdiv(hx.r * s.W, 16), hx.splits, st);
+      break;
+    case W_STEM_S2D:   // the stem on the space-to-depth kernel (conv_stem.inc): one slab per block
+      conv_arith_ref() = 6;
+      conv_note_kernel("stem_wgrad_s2d");
+      rc = stem_wgrad_s2d_launch(s, a, st);
+      break;
+    case W_STEM: {
+      conv_arith_ref() = 1;
+      conv_note_kernel("stem_wgrad");
+      const dim3 gs((unsigned)p.splits);
+      switch (s.Cin) {
+        case 1: hipLaunchKernelGGL(conv_wgrad_stem_kernel<1>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
+        case 2: hipLaunchKernelGGL(conv_wgrad_stem_kernel<2>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
+        case 3: hipLaunchKernelGGL(conv_wgrad_stem_kernel<3>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
+        case 4: hipLaunchKernelGGL(conv_wgrad_stem_kernel<4>, gs, dim3(256), 0, st, a); rc = MD2_OK; break;
+        default: break;
+      }
+      break;
     }
+    case W_WGRAD16:
+      conv_arith_ref() = 1;
+      conv_note_kernel("wgrad16");
+      grid.y = 1;
+      if (p.BM == 64) {
+        if (s.reflect)
+          hipLaunchKernelGGL((conv_wgrad16_kernel<4, 3, 3, 1>), grid, dim3(256), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv_wgrad16_kernel<4, 3, 3, 0>), grid, dim3(256), 0, st, a);
+      } else if (p.BM == 32) {
+        if (s.reflect)
+          hipLaunchKernelGGL((conv_wgrad16_kernel<2, 3, 3, 1>), grid, dim3(256), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv_wgrad16_kernel<2, 3, 3, 0>), grid, dim3(256), 0, st, a);
+      } else {
+        if (s.reflect)
+          hipLaunchKernelGGL((conv_wgrad16_kernel<1, 3, 3, 1>), grid, dim3(256), 0, st, a);
+        else
+          hipLaunchKernelGGL((conv_wgrad16_kernel<1, 3, 3, 0>), grid, dim3(256), 0, st, a);
+      }
+      rc = MD2_OK;
+      break;
+    default: rc = launch_w_tile(s, p, a, grid, st); break;
   }
-  if (rc == MD2_ENOTSUP && p.tile == W16x144) {
-    conv_arith_ref() = 1;
-    conv_note_kernel("wgrad16");
-    grid.y = 1;
-    if (p.BM == 64) {
-      if (s.reflect)
-        hipLaunchKernelGGL((conv_wgrad16_kernel<4, 3, 3, 1>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_wgrad16_kernel<4, 3, 3, 0>), grid, dim3(256), 0, st, a);
-    } else if (p.BM == 32) {
-      if (s.reflect)
-        hipLaunchKernelGGL((conv_wgrad16_kernel<2, 3, 3, 1>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_wgrad16_kernel<2, 3, 3, 0>), grid, dim3(256), 0, st, a);
-    } else {
-      if (s.reflect)
-        hipLaunchKernelGGL((conv_wgrad16_kernel<1, 3, 3, 1>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_wgrad16_kernel<1, 3, 3, 0>), grid, dim3(256), 0, st, a);
-    }
-    rc = MD2_OK;
-  }
-#define MD2_W_CASE(KS, SS, RR)                                                                     \
-  if (rc == MD2_ENOTSUP && s.KH == KS && s.stride == SS && s.reflect == RR) {                      \
-    switch (p.tile) {                                                                              \
-      case W32x256: rc = launch_w<32, 256, 1, 4, KS, SS, RR>(p.cw, a, grid, st); break;            \
-      case W64x64: rc = launch_w<64, 64, 2, 2, KS, SS, RR>(p.cw, a, grid, st); break;              \
-      case W32x128: rc = launch_w<32, 128, 1, 4, KS, SS, RR>(p.cw, a, grid, st); break;            \
-      case W64x192:                                                                                \
-        if constexpr (KS == 3) {                                                                   \
-          if (p.cw == 64) {                                                                        \
-            launch_w_cw<64, 192, 2, 2, KS, SS, RR, 64>(a, grid, st);                               \
-            rc = MD2_OK;                                                                           \
-          }                                                                                        \
-        }                                                                                          \
-        break;                                                                                     \
-      default: rc = launch_w<64, 128, 2, 2, KS, SS, RR>(p.cw, a, grid, st); break;                 \
-    }                                                                                              \
-  }
-  MD2_CONV_COMBOS(MD2_W_CASE)
-#undef MD2_W_CASE
-  if (rc) {
-    set_error("conv_wgrad: unsupported (kernel, stride, padding) combination");
-    return rc;
-  }
+  if (rc == MD2_ENOTSUP) set_error("conv_wgrad: unsupported (kernel, stride, padding) combination");
+  if (rc) return rc;
   MD2_LAUNCH_CHECK();
   WRed r{};
   r.slab = a.slab;
@@ -218,7 +226,7 @@ int conv_wgrad(const ConvShape& s, const TensorIn& x, const float* dy, float* dw
   r.dw = dw;
   r.acc = accumulate;
   r.ncols = (int)a.g.N;
-  r.tapc = (tap || hx.ok) ? s.Cin : 0;
+  r.tapc = (tap || rt.kind == W_WHALO) ? s.Cin : 0;
   r.KK = s.KH * s.KW;
   r.cinw = weight_cin(s);
   r.out_total = (long)s.Cout * r.cinw * r.KK;

@@ -1,7 +1,7 @@
 // Host-only check of csrc/conv_lds.h (tests/test_conv_lds.py compiles and runs it; no GPU, no
 // library): for every geometry a planner can see,
 //   fits  =>  need <= bytes <= cap          (a launch gets the LDS its kernel indexes)
-//   fits  ==  the planner's admission test as it was written out in the planners (now conv.hip) / conv_stem.inc
+//   fits  ==  the planner's admission test as it was written out in the planners (now conv_route.hip)
 //             before the geometry moved into the header (kept here literally: no planner
 //             decision changes)
 // and every bench-shape geometry is still admitted, the fixed sizes are the known ones.

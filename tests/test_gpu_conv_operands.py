@@ -35,6 +35,12 @@ form x family -> case id (test function[case])
                                            [16-16] (px), [head 64-1@4x13] (head_fallback),
                                            test_head_then_c1_dgrad (head_batched, then halo_rfl_dgrad
                                            accumulating into the head's dx)
+                     dgrad stride 2  px3   test_stride2_dgrad[1x1/2 64-128@8x12], [3x3/2 48-96@8x12] (the four
+                                           output-parity classes merged into one launch; taps 1 resp. 1/2/2/4
+                                           per class), [3x3/2 64-128@7x9] (odd H and W: four class launches
+                                           with unequal extents), test_accumulate_dgrad[64-128/2@7x9] (the same, +=)
+                                     px    test_stride2_dgrad[3x3/2 32-64@8x12] (Cin <= 32: the 32-row tile,
+                                           four class launches)
                      head shape, concat / split  test_head_shape_with_concat_or_split_runs_the_generic_kernels
                                            (px, wgrad16, px: the head kernels take one tensor only)
                      wgrad accumulate      test_accumulate_wgrad[64+64-64] (wgrad_px3 tile, one split),
@@ -348,6 +354,7 @@ ACC_DGRAD = {
     "16-16": (S(2, 16, 0, 6, 10, 16), "px"),                                  # Cin 16: the 32-row tile
     "64+64-64 split": (S(2, 64, 64, 6, 10, 64), "halo_rfl_dgrad"),            # both parts accumulate
     "head 64-1@4x13": (S(2, 64, 0, 4, 13, 1, act="sigmoid"), "head_fallback"),  # odd W (head2), strided dx +=
+    "64-128/2@7x9": (_plain(2, 64, 7, 9, 128, stride=2), "px3"),              # four class launches, each dx +=
 }
 
 
@@ -357,6 +364,22 @@ def test_accumulate_dgrad(name):
     errs, _ = _dgrad(sp, route, accumulate=True)
     for part, e in zip(("p0 rows", "p1 rows"), errs):
         _check("b", f"{name} dgrad += {part}", e)
+
+
+# the stride-2 data gradient off the stride-2 halo kernel: one dense GEMM per output-parity class
+S2_DGRAD = {
+    "1x1/2 64-128@8x12": (_plain(2, 64, 8, 12, 128, k=1, stride=2, pad=0), "px3"),   # merged classes, one tap
+    "3x3/2 48-96@8x12": (_plain(2, 48, 8, 12, 96, stride=2), "px3"),     # Cin % 64 != 0; merged, taps 1/2/2/4
+    "3x3/2 64-128@7x9": (_plain(2, 64, 7, 9, 128, stride=2), "px3"),     # odd H, W: four launches, unequal extents
+    "3x3/2 32-64@8x12": (_plain(2, 32, 8, 12, 64, stride=2), "px"),      # Cin <= 32: the 32-row tile
+}
+
+
+@pytest.mark.parametrize("name", list(S2_DGRAD))
+def test_stride2_dgrad(name):
+    sp, route = S2_DGRAD[name]
+    errs, _ = _dgrad(sp, route)
+    _check("b", f"{name} dgrad", errs[0])
 
 
 def test_head_then_c1_dgrad():
