@@ -1161,6 +1161,39 @@ int md2_automasking_loss_sources(int nsrc, const md2_loss_source* sources, const
                                  long long target_sample_stride, int n, int c, int h, int w,
                                  float* out, void* stream);
 
+/* Per-sample camera intrinsics.  Additive: MD2_ABI_VERSION is unchanged.
+ *
+ * md2_loss_fwd_bwd_sources_k is md2_loss_fwd_bwd_sources with sample i back-projected by invK[i] and
+ * projected by K[i]: K and invK are device [n][9] each (row-major 3x3 per sample, in the 1-based
+ * pixel coordinates of cfg->K), read and never written.  cfg->K / cfg->invK are not read.  The
+ * workspace is md2_loss_sources_workspace_size's.  Only the photometric warp (and vis_warped) reads
+ * intrinsics; the smoothness term, the automask and the reductions do not.  When every row of K /
+ * invK equals cfg->K / cfg->invK, every output equals md2_loss_fwd_bwd_sources' bit for bit (the
+ * arithmetic after the read is the same, operation for operation) -- and so, with two learned
+ * sources that are frames of x, md2_loss_fwd_bwd's.  It always runs on the kernel over sources,
+ * nsrc = 2 included.  The matrices are device data and are not validated.
+ * MD2_EINVAL (before any HIP call): a null K or invK, and everything md2_loss_fwd_bwd_sources
+ * checks. */
+int md2_loss_fwd_bwd_sources_k(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
+                               const float* target, long long target_sample_stride,
+                               const float* K, const float* invK,   /* device [n][9] each */
+                               const float* const* disp, const float* pose, const float* automask,
+                               float dloss, const md2_loss_out* out, void* workspace, void* stream);
+
+/* Per-sample intrinsics as model state, modelled on md2_model_set_disparity_bins: K and invK
+ * (device [batch][9] each) are copied into executor-owned buffers on `stream`, and every following
+ * forward_loss -- the plain, _aug and _stereo forms, md2_model_train_step, the train_step_graph
+ * family, md2_model_train_step_dp -- warps sample i with row i until they are set again.
+ * K == invK == NULL returns to cfg.K / cfg.invK.  While set, the loss tail runs as
+ * md2_loss_fwd_bwd_sources_k: the plain step over {src0, src1} learned, MS and S over their sources;
+ * the library's own automask is taken over the same sources.  With every row equal to cfg.K /
+ * cfg.invK the step's loss, gradient and parameters equal the plain step's bit for bit.  The
+ * captured graph reads the executor's buffers: it is captured again when intrinsics come or go, not
+ * when their values change.  Test mode is unaffected (inference reads no intrinsics).
+ * MD2_EINVAL: exactly one of K, invK null; a null model.  MPI mode (embedding_levels > 0):
+ * MD2_ENOTSUP when K is given. */
+int md2_model_set_intrinsics(md2_model* m, const float* K, const float* invK, void* stream);
+
 /* The training entry points with a stereo source, modelled on the _aug pair (x_net as there; NULL or
  * x: the networks read x).  x_stereo [batch][c][h][w] is the other camera's frame at the target's
  * time and stereo_Rt [batch][12] its fixed transform (R row-major, t).  The networks never see

@@ -838,10 +838,16 @@ function automasking_loss_sources(x::ROCArray{Float32,5}, x_stereo::ROCArray{Flo
     return out
 end
 
+# K / invK (both or neither): per-sample intrinsics, (9, n) each -- column i is sample i's 3x3 in
+# row-major order, vec(K_i') -- md2_loss_fwd_bwd_sources_k; cfg.K / cfg.invK are then not read
 function loss_tail_sources(cfg::LossCfg, disps, pose, x::ROCArray{Float32,5}, x_stereo::ROCArray{Float32,4},
                            stereo_Rt::ROCArray{Float32,2}, auto_loss; target_id=2, source_ids=(1, 3),
-                           temporal::Bool=true, dloss=1f0)
+                           temporal::Bool=true, dloss=1f0,
+                           K::Union{Nothing,ROCArray{Float32,2}}=nothing,
+                           invK::Union{Nothing,ROCArray{Float32,2}}=nothing)
     W, H, C, L, n = size(x); fs = W * H * C
+    (K === nothing) == (invK === nothing) || error("K and invK come together")
+    K === nothing || (size(K) == (9, n) && size(invK) == (9, n)) || error("K and invK must be (9,n) = ", (9, n))
     src = stereo_sources(x, x_stereo, stereo_Rt, target_id, source_ids, temporal)
     nsrc = length(src)
     loss = ROCVector{Float32}(undef, 1)
@@ -851,6 +857,14 @@ function loss_tail_sources(cfg::LossCfg, disps, pose, x::ROCArray{Float32,5}, x_
     out = LossOut(pointer(loss), C_NULL, ntuple(i -> i <= length(d_disp) ? pointer(d_disp[i]) : Ptr{Float32}(C_NULL), 5),
                   temporal ? pointer(d_pose) : C_NULL, C_NULL, C_NULL, C_NULL, C_NULL)
     dptrs = [pointer(d) for d in disps]
+    if K !== nothing
+        check(ccall((:md2_loss_fwd_bwd_sources_k, lib), Cint,
+                    (Ref{LossCfg}, Cint, Ptr{LossSource}, Ptr{Float32}, Clonglong, Ptr{Float32}, Ptr{Float32},
+                     Ptr{Ptr{Float32}}, Ptr{Float32}, Ptr{Float32}, Cfloat, Ref{LossOut}, Ptr{UInt8}, Ptr{Cvoid}),
+                    cfg, nsrc, src, pointer(x) + 4 * (target_id - 1) * fs, L * fs, K, invK, dptrs,
+                    temporal ? pointer(pose) : C_NULL, ptr(auto_loss), Float32(dloss), out, ws, stream_ptr()))
+        return loss, d_disp, d_pose
+    end
     check(ccall((:md2_loss_fwd_bwd_sources, lib), Cint,
                 (Ref{LossCfg}, Cint, Ptr{LossSource}, Ptr{Float32}, Clonglong, Ptr{Ptr{Float32}}, Ptr{Float32},
                  Ptr{Float32}, Cfloat, Ref{LossOut}, Ptr{UInt8}, Ptr{Cvoid}),
@@ -1154,6 +1168,23 @@ end
 function set_disparity_bins!(m::HIPModel, bins::ROCArray{Float32,2})
     check(ccall((:md2_model_set_disparity_bins, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}),
                 m.handle, bins, stream_ptr()))
+    return m
+end
+
+# Per-sample intrinsics of every following train_loss / train_step (plain, _aug, _stereo, graph, dp):
+# K, invK (9, batch) each, column i = sample i's 3x3 in row-major order (vec(K_i')), copied into
+# executor-owned buffers.  set_intrinsics!(m) returns to the ModelCfg's K.  The captured step is
+# captured again when intrinsics come or go, not when their values change.  Not in MPI mode.
+function set_intrinsics!(m::HIPModel, K::ROCArray{Float32,2}, invK::ROCArray{Float32,2})
+    (size(K) == (9, m.cfg.batch) && size(invK) == (9, m.cfg.batch)) ||
+        error("K and invK must be (9, batch) = ", (9, m.cfg.batch))
+    check(ccall((:md2_model_set_intrinsics, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                m.handle, K, invK, stream_ptr()))
+    return m
+end
+function set_intrinsics!(m::HIPModel)
+    check(ccall((:md2_model_set_intrinsics, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                m.handle, C_NULL, C_NULL, stream_ptr()))
     return m
 end
 

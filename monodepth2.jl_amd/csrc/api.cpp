@@ -159,10 +159,12 @@ size_t md2_loss_sources_workspace_size(const md2_loss_cfg* cfg, int nsrc) {
   return loss_tail_sources_workspace_bytes(to_tail_cfg(cfg), nsrc);
 }
 
-int md2_loss_fwd_bwd_sources(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
-                             const float* target, long long target_sample_stride,
-                             const float* const* disp, const float* pose, const float* automask,
-                             float dloss, const md2_loss_out* out, void* workspace, void* stream) {
+// the uniform and the per-sample (K, invK: device [n][9]) forms of the loss tail over sources
+static int loss_fwd_bwd_sources(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
+                                const float* target, long long target_sample_stride, const float* K,
+                                const float* invK, const float* const* disp, const float* pose,
+                                const float* automask, float dloss, const md2_loss_out* out,
+                                void* workspace, void* stream) {
   MD2_CHECK_ARG(cfg != nullptr && out != nullptr && out->loss != nullptr, "cfg/out/loss");
   MD2_CHECK_ARG(nsrc >= 1 && nsrc <= MD2_MAX_SOURCES, "nsrc must be 1, 2 or 3");
   MD2_CHECK_ARG(sources != nullptr, "sources: null pointer");
@@ -180,7 +182,25 @@ int md2_loss_fwd_bwd_sources(const md2_loss_cfg* cfg, int nsrc, const md2_loss_s
   o.vis_warped = out->vis_warped;
   o.vis_cell = out->vis_cell;
   return loss_tail_sources_run(to_tail_cfg(cfg), nsrc, src, target, (long)target_sample_stride, disp,
-                               pose, automask, dloss, o, workspace, (hipStream_t)stream);
+                               pose, automask, dloss, o, workspace, (hipStream_t)stream, K, invK);
+}
+
+int md2_loss_fwd_bwd_sources(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
+                             const float* target, long long target_sample_stride,
+                             const float* const* disp, const float* pose, const float* automask,
+                             float dloss, const md2_loss_out* out, void* workspace, void* stream) {
+  return loss_fwd_bwd_sources(cfg, nsrc, sources, target, target_sample_stride, nullptr, nullptr, disp, pose,
+                              automask, dloss, out, workspace, stream);
+}
+
+int md2_loss_fwd_bwd_sources_k(const md2_loss_cfg* cfg, int nsrc, const md2_loss_source* sources,
+                               const float* target, long long target_sample_stride, const float* K,
+                               const float* invK, const float* const* disp, const float* pose,
+                               const float* automask, float dloss, const md2_loss_out* out,
+                               void* workspace, void* stream) {
+  MD2_CHECK_ARG(K != nullptr && invK != nullptr, "per-sample intrinsics: null K or invK");
+  return loss_fwd_bwd_sources(cfg, nsrc, sources, target, target_sample_stride, K, invK, disp, pose,
+                              automask, dloss, out, workspace, stream);
 }
 
 int md2_automasking_loss_sources(int nsrc, const md2_loss_source* sources, const float* target,
@@ -680,6 +700,12 @@ int md2_model_profile_records(md2_model* m, int max, double* ms, double* work, i
 int md2_model_set_disparity_bins(md2_model* m, const float* bins, void* stream) {
   MD2_CHECK_ARG(m, "model");
   return model_set_bins(m->impl, bins, (hipStream_t)stream);
+}
+
+int md2_model_set_intrinsics(md2_model* m, const float* K, const float* invK, void* stream) {
+  MD2_CHECK_ARG((K == nullptr) == (invK == nullptr), "set_intrinsics: K and invK come together (both null clears)");
+  MD2_CHECK_ARG(m, "model");
+  return model_set_intrinsics(m->impl, K, invK, (hipStream_t)stream);
 }
 
 int md2_model_outputs(md2_model* m, const float** disp, int* w, int* h, const float** pose) {

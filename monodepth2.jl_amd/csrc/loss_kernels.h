@@ -70,6 +70,10 @@ struct PhotoSrcArgs {
   float wloss;
   const float* gmap;            // [N][H][W] per-pixel cotangent (times wloss) or nullptr
   int N;
+  // per-sample intrinsics: device [N][9] each, row-major, read only; both or neither.  Set, sample
+  // i is warped by Kn + 9 i / invKn + 9 i and Geom's K / invK are not read
+  const float* Kn;
+  const float* invKn;
 };
 
 // Wave tiling of the photometric pass (photo.hip): 60 output columns x `rows` output rows per

@@ -580,13 +580,24 @@ int launch_so3_bwd(const float* pose, int count, int N, int invert_mask, const f
 // through the scale's depth and pose, no loss, no backward.  One thread per target pixel, all C
 // channels of all S sources; same geometry helpers as the photometric kernels.  out [S][N][C][H][W]
 template <int C, int S>
-__global__ __launch_bounds__(256) void warp_vis_kernel(PhotoSrcArgs a, int scale, Geom g,
+__global__ __launch_bounds__(256) void warp_vis_kernel(PhotoSrcArgs a, int scale, Geom gu,
                                                        float* __restrict__ out) {
   const PhotoScale sc = a.sc[scale];
+  // g: the geometry this pixel is warped with -- the kernel argument, or with per-sample
+  // intrinsics (a.Kn) a copy holding the pixel's sample's matrices.  The arithmetic below is the
+  // same either way, so without a.Kn the kernel gives the bits it gave before a.Kn existed.
+  Geom g = gu;
   const int HW = g.W * g.H;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long)a.N * HW) return;
   const int n = (int)(idx / HW), pix = (int)(idx - (long)n * HW);
+  if (a.Kn) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      g.K[i] = a.Kn[9 * (long)n + i];
+      g.invK[i] = a.invKn[9 * (long)n + i];
+    }
+  }
   const int Y = pix / g.W, X = pix - Y * g.W;
   const float d = disp_at(sc.disp + (long)n * sc.dw * sc.dh, sc.dw, sc.dh, sc.rx, sc.ry, g.W, g.H, X, Y);
   const float depth = 1.f / (d * g.disp_range + g.min_disp);

@@ -64,9 +64,12 @@ int check_scale_dims(const LossTailCfg& c) {
 
 // The loss tail over S sources.  x != nullptr: the sources and the target are frames c.src0 /
 // c.src1 / c.target of x, and the photometric pass is the packed two-source kernel (photo.hip);
-// otherwise it is the kernel over sources (photo_sources.hip).  Everything else is one sequence.
+// otherwise it is the kernel over sources (photo_sources.hip).  Kn / invKn (device [N][9] each, both
+// or neither, sources form only): per-sample intrinsics, c.K / c.invK are then not read by any
+// kernel.  Everything else is one sequence.
 int run(const LossTailCfg& c, int S, const LossSource* src, const float* target,
-        long target_sample_stride, const float* x, const float* const* disp, const float* pose,
+        long target_sample_stride, const float* x, const float* Kn, const float* invKn,
+        const float* const* disp, const float* pose,
         const float* automask, float dloss, const LossTailOut& o, void* workspace, hipStream_t st) {
   MD2_CHECK_ARG(S >= 1 && S <= MAX_SOURCES, "nsrc must be 1, 2 or 3");
   MD2_CHECK_ARG(src != nullptr, "sources: null pointer");
@@ -74,6 +77,8 @@ int run(const LossTailCfg& c, int S, const LossSource* src, const float* target,
   MD2_CHECK_ARG(c.nscales >= 1 && c.nscales <= MAX_SCALES, "nscales");
   MD2_CHECK_ARG(c.C == 1 || c.C == 3, "channels must be 1 or 3");
   MD2_CHECK_ARG(workspace != nullptr && disp != nullptr && target != nullptr, "null pointer");
+  MD2_CHECK_ARG((Kn == nullptr) == (invKn == nullptr) && !(x && Kn),
+                "per-sample intrinsics: K and invK come together, on the sources form");
   // the learned sources' blocks of `pose` are 0..n_learned-1, each once
   int n_learned = 0, seen = 0, invert_mask = 0;
   bool in_place = true;     // every learned source s has pose block s: composeT writes Rt itself
@@ -140,6 +145,8 @@ int run(const LossTailCfg& c, int S, const LossSource* src, const float* target,
   pa.automask = automask;
   pa.wloss = up / ((float)c.N * c.W * c.H);
   pa.N = c.N;
+  pa.Kn = Kn;
+  pa.invKn = invKn;
   const size_t plane = (size_t)c.N * c.W * c.H;
   DispSumBatch db{};
   db.W = c.W;
@@ -263,9 +270,9 @@ size_t loss_tail_sources_workspace_bytes(const LossTailCfg& c, int nsrc) {
 int loss_tail_sources_run(const LossTailCfg& c, int S, const LossSource* src, const float* target,
                           long target_sample_stride, const float* const* disp, const float* pose,
                           const float* automask, float dloss, const LossTailOut& o, void* workspace,
-                          hipStream_t st) {
-  return run(c, S, src, target, target_sample_stride, nullptr, disp, pose, automask, dloss, o,
-             workspace, st);
+                          hipStream_t st, const float* Kn, const float* invKn) {
+  return run(c, S, src, target, target_sample_stride, nullptr, Kn, invKn, disp, pose, automask, dloss,
+             o, workspace, st);
 }
 
 // the two sources are frames c.src0 / c.src1 of x, learned, with pose blocks 0 and 1
@@ -276,8 +283,8 @@ int loss_tail_run(const LossTailCfg& c, const float* const* disp, const float* p
   const LossSource src[2] = {
       {x + c.src0 * c.x_frame_stride, c.x_sample_stride, 0, c.invert_mask & 1, nullptr},
       {x + c.src1 * c.x_frame_stride, c.x_sample_stride, 1, (c.invert_mask >> 1) & 1, nullptr}};
-  return run(c, 2, src, x + c.target * c.x_frame_stride, c.x_sample_stride, x, disp, pose, automask,
-             dloss, o, workspace, st);
+  return run(c, 2, src, x + c.target * c.x_frame_stride, c.x_sample_stride, x, nullptr, nullptr, disp,
+             pose, automask, dloss, o, workspace, st);
 }
 
 

@@ -62,10 +62,13 @@ size_t loss_tail_sources_workspace_bytes(const LossTailCfg& c, int nsrc);
 // o.vis_sel holds 0..nsrc-1 or -1.  The learned sources' pose blocks must be 0..n_learned-1, each
 // once; with the learned sources first and in block order composeT writes and reads Rt / dRt in
 // place, any other order stages its rows through copies.
+// Kn / invKn: per-sample intrinsics, device [N][9] each (row-major, read only), both or neither.
+// Set, sample i is warped by Kn + 9 i / invKn + 9 i and c.K / c.invK are not read; rows all equal
+// to c.K / c.invK give the bits of the call without them.
 int loss_tail_sources_run(const LossTailCfg& c, int nsrc, const LossSource* src, const float* target,
                           long target_sample_stride, const float* const* disp, const float* pose,
                           const float* automask, float dloss, const LossTailOut& o, void* workspace,
-                          hipStream_t st);
+                          hipStream_t st, const float* Kn = nullptr, const float* invKn = nullptr);
 
 // Op-level per-scale warp + photometric loss (md2_warp_photometric_*).
 struct WarpOpCfg {

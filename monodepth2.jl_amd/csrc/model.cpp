@@ -195,6 +195,7 @@ static int capture_step(Model* m, bool with_auto, bool with_net, float* adam_m, 
   g.with_auto = with_auto ? 1 : 0;
   g.with_net = with_net ? 1 : 0;
   g.stereo_mode = stereo_mode;
+  g.intrinsics = m->intr_on ? 1 : 0;
   g.guard_on = m->gd.on ? 1 : 0;
   g.guard_max = m->gd.max_norm;
   g.next_step = -1;
@@ -225,7 +226,8 @@ static int train_step_graph_impl(Model* m, const float* x, const float* x_net, c
   // pending per-segment updates (outside the capture: the event lives outside the graph)
   MD2_TRY(m->adam_join(st));
   if (!g.exec || g.adam_m != adam_m || g.adam_v != adam_v || g.lr != lr || g.with_auto != (int)with_auto ||
-      g.with_net != (int)with_net || g.stereo_mode != stereo_mode || g.guard_on != (int)m->gd.on ||
+      g.with_net != (int)with_net || g.stereo_mode != stereo_mode || g.intrinsics != (int)m->intr_on ||
+      g.guard_on != (int)m->gd.on ||
       (m->gd.on && g.guard_max != m->gd.max_norm))
     MD2_TRY(capture_step(m, with_auto, with_net, adam_m, adam_v, lr, stereo_mode));
   const size_t xb = sizeof(float) * (size_t)m->N * 3 * m->cfg.arch.in_ch * m->cfg.H * m->cfg.W;
@@ -579,6 +581,29 @@ int model_set_bins(Model* m, const float* bins, hipStream_t st) {
     return MD2_ESTATE;
   }
   MD2_HIP(hipMemcpyAsync(m->bins, bins, sizeof(float) * m->N * m->NP, hipMemcpyDefault, st));
+  return MD2_OK;
+}
+
+int model_set_intrinsics(Model* m, const float* K, const float* invK, hipStream_t st) {
+  MD2_CHECK_ARG((K == nullptr) == (invK == nullptr), "set_intrinsics: K and invK come together (both null clears)");
+  MD2_CHECK_ARG(m, "model");
+  if (!K) {
+    m->intr_on = false;
+    return MD2_OK;
+  }
+  if (m->E > 0) {
+    set_error("set_intrinsics: per-sample intrinsics are not supported in MPI mode (embedding_levels > 0)");
+    return MD2_ENOTSUP;
+  }
+  if (!m->Kn) {
+    MD2_TRY(m->alloc(&m->Kn, (size_t)m->N * 9));
+    MD2_TRY(m->alloc(&m->invKn, (size_t)m->N * 9));
+  }
+  MD2_TRY(m->ensure_stereo_ws());   // the sources form's workspace and the automask buffer
+  const size_t b = sizeof(float) * (size_t)m->N * 9;
+  MD2_HIP(hipMemcpyAsync(m->Kn, K, b, hipMemcpyDeviceToDevice, st));
+  MD2_HIP(hipMemcpyAsync(m->invKn, invK, b, hipMemcpyDeviceToDevice, st));
+  m->intr_on = true;
   return MD2_OK;
 }
 

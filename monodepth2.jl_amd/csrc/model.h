@@ -101,6 +101,8 @@ int model_train_step_graph_aug(Model* m, const float* x, const float* x_net, con
                                float* adam_m, float* adam_v, float lr, int step, float* loss, hipStream_t st);
 // MPI mode: the disparity bins [N][num_bins] of the next forwards (device; copied)
 int model_set_bins(Model* m, const float* bins, hipStream_t st);
+// per-sample intrinsics (md2.h, md2_model_set_intrinsics): K / invK device [N][9], both null clears
+int model_set_intrinsics(Model* m, const float* K, const float* invK, hipStream_t st);
 // outputs of the last forward
 int model_outputs(Model* m, const float** disp, int* dw, int* dh, const float** pose);
 // the five encoder stage outputs of the last forward: [3N frame-major images][c][h][w]

@@ -374,15 +374,17 @@ int Model::forward_loss(const float* x, const float* x_net, const float* automas
     for (int k = 0; k < 2; ++k) pev[k] = pf.ev();
     o.photo_events = pev;
   }
-  if (stereo) {
+  // the sources form of the tail: a stereo source, or per-sample intrinsics (set_intrinsics), which
+  // always run on the kernel over sources -- M is then {src0, src1} learned
+  if (stereo || intr_on) {
     const long fs = tail.x_frame_stride, ss = tail.x_sample_stride;
     LossSource src[MAX_SOURCES];
     int S = 0;
-    if (stereo->temporal) {
+    if (!stereo || stereo->temporal) {
       src[S++] = LossSource{x + tail.src0 * fs, ss, 0, tail.invert_mask & 1, nullptr};
       src[S++] = LossSource{x + tail.src1 * fs, ss, 1, (tail.invert_mask >> 1) & 1, nullptr};
     }
-    src[S++] = LossSource{stereo->x, fs, -1, 0, stereo->Rt};
+    if (stereo) src[S++] = LossSource{stereo->x, fs, -1, 0, stereo->Rt};
     const float* target = x + tail.target * fs;
     if (cfg.automask && !automask) {   // over the same sources the loss uses
       const float* fr[MAX_SOURCES];
@@ -396,9 +398,9 @@ int Model::forward_loss(const float* x, const float* x_net, const float* automas
     }
     // S: no learned source, so the tail writes no d_pose; the pose network still runs its backward
     // (the segments, the DP buckets and the graph keep their shape) on a zero cotangent
-    if (!stereo->temporal) MD2_HIP(hipMemsetAsync(d_pose, 0, sizeof(float) * 2 * N * 6, st));
+    if (stereo && !stereo->temporal) MD2_HIP(hipMemsetAsync(d_pose, 0, sizeof(float) * 2 * N * 6, st));
     MD2_TRY(loss_tail_sources_run(tail, S, src, target, ss, disps, pose, cfg.automask ? automask : nullptr, 1.f,
-                                  o, tail_src_ws, st));
+                                  o, tail_src_ws, st, intr_on ? Kn : nullptr, intr_on ? invKn : nullptr));
     if (pf.on) {
       const double bytes = (double)tail.nscales * ND * cfg.H * cfg.W * (8.0 + 4.0 * (1 + S) * cfg.arch.in_ch);
       pf.recs.push_back({pev[0], pev[1], PROF_PHOTO, bytes, "photometric over sources (all scales)"});

@@ -203,6 +203,7 @@ struct StepGraph {
   float *x = nullptr, *x_net = nullptr, *autoloss = nullptr, *loss = nullptr, *bc = nullptr;
   float *x_stereo = nullptr, *stereo_Rt = nullptr;   // train_step_graph_stereo's input copies
   int stereo_mode = -1;   // part of the capture: 0 no stereo source, 1 MS (temporal), 2 S
+  int intrinsics = -1;    // so is whether per-sample intrinsics are set (their values are not)
   int* step = nullptr;
   float *adam_m = nullptr, *adam_v = nullptr;
   float lr = 0.f;
@@ -300,6 +301,10 @@ class Model {
   void* tail_ws = nullptr;
   void* tail_src_ws = nullptr;  // the sources form's workspace (3 sources), allocated at first use
   int ensure_stereo_ws();
+  // per-sample intrinsics (md2_model_set_intrinsics): executor-owned [N][9] copies, allocated at the
+  // first set; while intr_on every forward_loss runs the sources form of the loss tail with them
+  float *Kn = nullptr, *invKn = nullptr;
+  bool intr_on = false;
   float* loss_buf = nullptr;
   float* amask = nullptr;       // automasking_loss of the current batch when the caller passes none
   // Running statistics of every BatchNorm in ONE flat vector (the layout of

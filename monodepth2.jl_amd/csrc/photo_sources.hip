@@ -23,7 +23,13 @@
 
 namespace md2 {
 
-template <int C, int S, bool CELLS>
+//
+// PK (per-sample intrinsics): the camera matrices of the block's sample come from a.Kn / a.invKn
+// (device [N][9] each, read only) instead of g.K / g.invK.  They are read where g.K / g.invK are --
+// the prologue and the Kc products of the partials -- through Kat / iKat below; a block belongs to
+// one sample, so the loads are uniform.  Every operation after the read is the same, so equal rows
+// give the PK = false instance's bits.
+template <int C, int S, bool CELLS, bool PK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 3 ? 1 : 2)))
 void photo_sources_kernel(PhotoSrcArgs a, Geom g, PhotoTiling tl) {
   constexpr int NV = 2 * C * S + 1;   // parked P1 state: d val / d ix, d val / d iy (C S each), depth
@@ -56,32 +62,63 @@ void photo_sources_kernel(PhotoSrcArgs a, Geom g, PhotoTiling tl) {
   const __amdgpu_buffer_rsrc_t rdsp =
       make_rsrc(sc.disp + (long)n * dw * dh, (uint32_t)dw * dh * 4u);
 
+  [[maybe_unused]] const float* Kn = nullptr;
+  [[maybe_unused]] const float* iKn = nullptr;
+  if constexpr (PK) {
+    Kn = a.Kn + 9 * (long)n;
+    iKn = a.invKn + 9 * (long)n;
+  }
+  auto Kat = [&](int i) -> float {
+    if constexpr (PK)
+      return Kn[i];
+    else
+      return g.K[i];
+  };
+  auto iKat = [&](int i) -> float {
+    if constexpr (PK)
+      return iKn[i];
+    else
+      return g.invK[i];
+  };
+
   // pixel -> camera maps per source in centred coordinates, formed in fp64 once per (sample, source)
   // and rounded once (photo.hip).  s_cam[3 sp + i] = Mc row i (x, y, z) and Kct_i of source sp;
   // s_cam[3 S + i] = invK S row i; s_cam[3 S + 3 + sp] = the depth-derivative constants of sp
-  const float cxp = vreg(g.K[2]), cyp = vreg(g.K[5]);
+  const float cxp = vreg(Kat(2)), cyp = vreg(Kat(5));
+  // Kc is only read by the partials at the end.  From kernel arguments it is rematerialised there;
+  // from memory (PK) it would stay in nine registers for the whole kernel, so it is formed there
   float Kc[9];
+  auto make_Kc = [&]() {
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    Kc[j] = fmaf(-cxp, g.K[6 + j], g.K[j]);
-    Kc[3 + j] = fmaf(-cyp, g.K[6 + j], g.K[3 + j]);
-    Kc[6 + j] = g.K[6 + j];
-  }
+    for (int j = 0; j < 3; ++j) {
+      Kc[j] = fmaf(-cxp, Kat(6 + j), Kat(j));
+      Kc[3 + j] = fmaf(-cyp, Kat(6 + j), Kat(3 + j));
+      Kc[6 + j] = Kat(6 + j);
+    }
+  };
+  if constexpr (!PK) make_Kc();
+  // row i (a lane's own) of a 3x3 held in registers: PK selects it, so the tables never go to scratch
+  auto rowel = [&](const double (&A)[9], int i, int j) -> double {
+    if constexpr (PK)
+      return i == 0 ? A[j] : (i == 1 ? A[3 + j] : A[6 + j]);
+    else
+      return A[3 * i + j];
+  };
   __shared__ float4 s_cam[4 * S + 3];
   if (lane < 4 * S + 3) {
-    const double cxd = g.K[2], cyd = g.K[5];
+    const double cxd = Kat(2), cyd = Kat(5);
     double Kd[9], iKS[9];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      Kd[j] = (double)g.K[j] - cxd * g.K[6 + j];
-      Kd[3 + j] = (double)g.K[3 + j] - cyd * g.K[6 + j];
-      Kd[6 + j] = g.K[6 + j];
+      Kd[j] = (double)Kat(j) - cxd * Kat(6 + j);
+      Kd[3 + j] = (double)Kat(3 + j) - cyd * Kat(6 + j);
+      Kd[6 + j] = Kat(6 + j);
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      iKS[3 * i] = g.invK[3 * i];
-      iKS[3 * i + 1] = g.invK[3 * i + 1];
-      iKS[3 * i + 2] = (double)g.invK[3 * i] * cxd + (double)g.invK[3 * i + 1] * cyd + g.invK[3 * i + 2];
+      iKS[3 * i] = iKat(3 * i);
+      iKS[3 * i + 1] = iKat(3 * i + 1);
+      iKS[3 * i + 2] = (double)iKat(3 * i) * cxd + (double)iKat(3 * i + 1) * cyd + iKat(3 * i + 2);
     }
     float4 v;
     if (lane < 3 * S) {
@@ -90,14 +127,14 @@ void photo_sources_kernel(PhotoSrcArgs a, Geom g, PhotoTiling tl) {
       double KR[3], m[3];
 #pragma unroll
       for (int j = 0; j < 3; ++j)
-        KR[j] = Kd[3 * i] * rt[j] + Kd[3 * i + 1] * rt[3 + j] + Kd[3 * i + 2] * rt[6 + j];
+        KR[j] = rowel(Kd, i, 0) * rt[j] + rowel(Kd, i, 1) * rt[3 + j] + rowel(Kd, i, 2) * rt[6 + j];
 #pragma unroll
       for (int j = 0; j < 3; ++j) m[j] = KR[0] * iKS[j] + KR[1] * iKS[3 + j] + KR[2] * iKS[6 + j];
-      const double kt = Kd[3 * i] * rt[9] + Kd[3 * i + 1] * rt[10] + Kd[3 * i + 2] * rt[11];
+      const double kt = rowel(Kd, i, 0) * rt[9] + rowel(Kd, i, 1) * rt[10] + rowel(Kd, i, 2) * rt[11];
       v = make_float4((float)m[0], (float)m[1], (float)m[2], (float)kt);
     } else if (lane < 3 * S + 3) {
       const int r = lane - 3 * S;
-      v = make_float4((float)iKS[3 * r], (float)iKS[3 * r + 1], (float)iKS[3 * r + 2], 0.f);
+      v = make_float4((float)rowel(iKS, r, 0), (float)rowel(iKS, r, 1), (float)rowel(iKS, r, 2), 0.f);
     } else {
       const int q = lane - (3 * S + 3);
       const float* rt = a.Rt + ((long)q * a.N + n) * 12;
@@ -490,6 +527,7 @@ void photo_sources_kernel(PhotoSrcArgs a, Geom g, PhotoTiling tl) {
 #pragma unroll
   for (int i = 0; i < 12 * S; ++i) acc[i] = wave_sum_dpp(acc[i]);
   if (lane == 0) {
+    if constexpr (PK) make_Kc();
     float* out = sc.partials + (((long)n * tl.tiles_y + ty) * tl.tiles_x + tx) * PS;
     out[0] = lsum;
 #pragma unroll
@@ -508,24 +546,24 @@ void photo_sources_kernel(PhotoSrcArgs a, Geom g, PhotoTiling tl) {
 }
 
 namespace {
-template <int C, int S>
+template <int C, int S, bool PK>
 void launch_cs(const PhotoSrcArgs& a, const Geom& g, const PhotoTiling& tl, bool cells, long blocks,
                hipStream_t st) {
   const dim3 grid((unsigned)blocks), block(64);
   if (cells)
-    hipLaunchKernelGGL((photo_sources_kernel<C, S, true>), grid, block, 0, st, a, g, tl);
+    hipLaunchKernelGGL((photo_sources_kernel<C, S, true, PK>), grid, block, 0, st, a, g, tl);
   else
-    hipLaunchKernelGGL((photo_sources_kernel<C, S, false>), grid, block, 0, st, a, g, tl);
+    hipLaunchKernelGGL((photo_sources_kernel<C, S, false, PK>), grid, block, 0, st, a, g, tl);
 }
-template <int C>
+template <int C, bool PK>
 void launch_c(const PhotoSrcArgs& a, const Geom& g, const PhotoTiling& tl, bool cells, long blocks,
               hipStream_t st) {
   if (a.nsrc == 1)
-    launch_cs<C, 1>(a, g, tl, cells, blocks, st);
+    launch_cs<C, 1, PK>(a, g, tl, cells, blocks, st);
   else if (a.nsrc == 2)
-    launch_cs<C, 2>(a, g, tl, cells, blocks, st);
+    launch_cs<C, 2, PK>(a, g, tl, cells, blocks, st);
   else
-    launch_cs<C, 3>(a, g, tl, cells, blocks, st);
+    launch_cs<C, 3, PK>(a, g, tl, cells, blocks, st);
 }
 }  // namespace
 
@@ -537,10 +575,12 @@ int launch_photometric_sources(const PhotoSrcArgs& a, const Geom& g, int C, hipS
   for (int s = 0; s < a.nsrc; ++s) MD2_CHECK_ARG(a.src[s] != nullptr, "photometric: null source");
   const PhotoTiling tl = photo_tiling(g.W, g.H, a.N, a.nscales);
   const long blocks = tl.per_scale() * a.N * a.nscales;
+  MD2_CHECK_ARG((a.Kn == nullptr) == (a.invKn == nullptr), "photometric: Kn and invKn come together");
+  const bool pk = a.Kn != nullptr;
   if (C == 3)
-    launch_c<3>(a, g, tl, cells, blocks, st);
+    pk ? launch_c<3, true>(a, g, tl, cells, blocks, st) : launch_c<3, false>(a, g, tl, cells, blocks, st);
   else
-    launch_c<1>(a, g, tl, cells, blocks, st);
+    pk ? launch_c<1, true>(a, g, tl, cells, blocks, st) : launch_c<1, false>(a, g, tl, cells, blocks, st);
   MD2_LAUNCH_CHECK();
   return MD2_OK;
 }

@@ -258,6 +258,7 @@ _SIGS = {
     "md2_model_get_grads": (C.c_int, [P, P, P]),
     "md2_model_loss_cotangent": (C.c_int, [P, C.c_float, P]),
     "md2_model_set_disparity_bins": (C.c_int, [P, P, P]),
+    "md2_model_set_intrinsics": (C.c_int, [P, P, P, P]),
     "md2_model_outputs": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                     C.POINTER(C.c_void_p)]),
     "md2_model_eval_disparity": (C.c_int, [P, P, C.c_int, C.POINTER(C.c_void_p), P]),
@@ -325,6 +326,8 @@ _SIGS = {
     "md2_loss_sources_workspace_size": (C.c_size_t, [C.POINTER(LossCfg), C.c_int]),
     "md2_loss_fwd_bwd_sources": (C.c_int, [C.POINTER(LossCfg), C.c_int, C.POINTER(LossSource), P, C.c_longlong,
                                            FP, P, P, C.c_float, C.POINTER(LossOut), P, P]),
+    "md2_loss_fwd_bwd_sources_k": (C.c_int, [C.POINTER(LossCfg), C.c_int, C.POINTER(LossSource), P, C.c_longlong,
+                                             P, P, FP, P, P, C.c_float, C.POINTER(LossOut), P, P]),
     "md2_automasking_loss_sources": (C.c_int, [C.c_int, C.POINTER(LossSource), P, C.c_longlong, C.c_int, C.c_int,
                                                C.c_int, C.c_int, P, P]),
     "md2_model_forward_loss_stereo": (C.c_int, [P, P, P, P, P, C.c_int, P, P, P, P]),
@@ -339,6 +342,8 @@ _SIGS = {
 # the sources (stereo) entry points, added without an ABI bump
 _SOURCES_SYMS = ("md2_loss_sources_workspace_size", "md2_loss_fwd_bwd_sources", "md2_automasking_loss_sources",
                  "md2_model_forward_loss_stereo", "md2_model_train_step_graph_stereo")
+# per-sample intrinsics, added the same way
+_INTRINSICS_SYMS = ("md2_loss_fwd_bwd_sources_k", "md2_model_set_intrinsics")
 _BN_EX_SYMS = ("md2_maxpool3s2_bwd_ex", "md2_bn_ex_workspace_size", "md2_bn_channel_fits", "md2_bn_forward_ex",
                "md2_bn_backward_ex")
 
@@ -355,7 +360,7 @@ def lib():
     import torch  # noqa: F401
     l = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in _SIGS.items():
-        if name in _SOURCES_SYMS + _BN_EX_SYMS and os.environ.get("MD2HIP_LIB") is not None and not hasattr(l, name):
+        if name in _SOURCES_SYMS + _INTRINSICS_SYMS + _BN_EX_SYMS and os.environ.get("MD2HIP_LIB") is not None and not hasattr(l, name):
             continue     # an older library given for an A/B: it has no such entry points to call
         f = getattr(l, name)
         f.restype = res

@@ -95,9 +95,12 @@ def backward_allreduce(executor, comm: Comm | None):
           "md2_model_backward_allreduce")
 
 
-def train_step_dp(executor, model, opt, x, comm: Comm | None, loss=None):
-    """forward_loss -> backward with bucketed RCCL all-reduce -> ADAM(grad_scale = 1/nranks)."""
-    out = executor.forward_loss(x, None, loss=loss)
+def train_step_dp(executor, model, opt, x, comm: Comm | None, loss=None, K=None, invK=None):
+    """forward_loss -> backward with bucketed RCCL all-reduce -> ADAM(grad_scale = 1/nranks).
+    ``K`` / ``invK``: this rank's per-sample intrinsics, as ``train_loss``; like every call through
+    ``forward_loss``, a call without them clears what an earlier call set on the executor."""
+    intr = {} if K is None and invK is None else dict(K=K, invK=invK)
+    out = executor.forward_loss(x, None, loss=loss, **intr)
     backward_allreduce(executor, comm)
     opt.update(model, grad_scale=comm.grad_scale if comm else 1.0)
     return out

@@ -162,6 +162,18 @@ class _Dataset:
             return np.array([np.random.default_rng((seed, i)).random() < a.p for i in idx], dtype=np.uint8)
         return None
 
+    def intrinsics(self, idx) -> np.ndarray:
+        """The camera matrix of every sample of ``idx``: float64 [len(idx), 3, 3] (the dataset's K)."""
+        return np.repeat(np.asarray(self.K, dtype=np.float64)[None], len(idx), 0)
+
+    def flip_coins(self, idx, seed: int = 0) -> np.ndarray:
+        """Whether FlipX mirrors each sample of ``idx`` under ``seed`` (the draws of getobs / batch_u8):
+        uint8 [len(idx)].  ValueError for augmentations other than nothing or one FlipX."""
+        coins = self._native_flips(list(idx), seed)
+        if coins is None:
+            raise ValueError("flip_coins knows no augmentation but FlipX")
+        return coins
+
     def batch_u8(self, idx, seed: int = 0, threads: int = 8, out=None):
         """Samples ``idx`` as one uint8 [n][3][C][H][W] array, decoded by the library's native
         loader on ``threads`` host threads (md2_load_*_u8); the per-sample Python path when the
@@ -417,6 +429,21 @@ class DChain:
     def slot_bytes(self):
         return max(d.slot_bytes for d in self.datasets)
 
+    def intrinsics(self, idx) -> np.ndarray:
+        """The camera matrix of every sample of ``idx``, its member dataset's K: float64
+        [len(idx), 3, 3].  The members of a chain need not share a camera."""
+        out = np.zeros((len(idx), 3, 3), dtype=np.float64)
+        for bid, items in self._groups(idx).items():
+            out[[k for k, _ in items]] = self.datasets[bid].intrinsics([li for _, li in items])
+        return out
+
+    def flip_coins(self, idx, seed: int = 0) -> np.ndarray:
+        """The members' FlipX coins of samples ``idx`` (a member draws by its own sample index)."""
+        out = np.zeros(len(idx), dtype=np.uint8)
+        for bid, items in self._groups(idx).items():
+            out[[k for k, _ in items]] = self.datasets[bid].flip_coins([li for _, li in items], seed)
+        return out
+
     def batch_native(self, idx, seed: int = 0, threads: int = 8, out=None):
         """Per member dataset one native decode into its own stretch of ``out``; offsets, sizes and
         flips come back in ``idx`` order (every image carries its own offset)."""
@@ -491,17 +518,27 @@ class DataLoader:
     ``(x, x_stereo, stereo_Rt)`` -- or ``(x, x_net, x_stereo, stereo_Rt)`` with ``color_jitter`` --
     where x_stereo [N][C][H][W] is the partner camera's frame at the target's index, resized and
     mirrored with its sample, and stereo_Rt [N][12] is ``md2hip.stereo_transforms`` of the dataset's
-    side and the samples' FlipX coins.  Colour jitter does not touch x_stereo: only the loss reads it."""
+    side and the samples' FlipX coins.  Colour jitter does not touch x_stereo: only the loss reads it.
+    ``intrinsics=True``: the loader appends ``K, invK`` (float32 [N][9] each, on ``device``) to whatever
+    it yields otherwise -- ``(x, K, invK)``, ``(x, x_net, K, invK)``, ... -- the per-sample camera
+    matrices that ``train_loss`` / ``train_step`` take as ``K=`` / ``invK=``: row i is
+    ``dataset.intrinsics`` of sample i (in a ``DChain``, its member's K), and for a sample that FlipX
+    mirrored ``cx' = W + 1 - cx`` (K is in the 1-based pixel coordinates of Backproject, whose image
+    centre is (W + 1) / 2).  invK is the fp64 inverse of that K, rounded once."""
 
     def __init__(self, dataset, batch_size: int, *, shuffle: bool = True, seed: int = 0,
                  workers: int = 8, device=None, rank: int = 0, world: int = 1, prefetch: int = 2,
-                 bytes_h2d: bool = True, native: bool = True, color_jitter=None, stereo: bool = False):
+                 bytes_h2d: bool = True, native: bool = True, color_jitter=None, stereo: bool = False,
+                 intrinsics: bool = False):
         if stereo and getattr(dataset, "resize", "host") != "device":
             raise ValueError('stereo=True needs a dataset with resize="device" (the partner frame rides the '
                              "device route)")
         if bool(stereo) != bool(getattr(dataset, "stereo", False)):
             raise ValueError("DataLoader(stereo=...) and the dataset's stereo= must agree")
         self.stereo = bool(stereo)
+        self.intrinsics = bool(intrinsics)
+        if self.intrinsics and not (hasattr(dataset, "intrinsics") and hasattr(dataset, "flip_coins")):
+            raise ValueError("intrinsics=True needs a dataset with intrinsics(idx) and flip_coins(idx, seed)")
         self.ds, self.batch_size, self.shuffle, self.seed = dataset, batch_size, shuffle, seed
         self.workers, self.rank, self.world, self.prefetch = workers, rank, world, prefetch
         self.bytes_h2d, self.native = bytes_h2d, native
@@ -523,6 +560,14 @@ class DataLoader:
         gb = self.batch_size * self.world
         lo, hi = shard_range(gb, self.world, self.rank)
         return [order[b * gb + lo:b * gb + hi].tolist() for b in range(len(order) // gb)]
+
+    def batch_intrinsics(self, idx, epoch: int):
+        """(K, invK) of samples ``idx`` as drawn in ``epoch``: float32 [len(idx), 9] NumPy arrays."""
+        K = np.array(self.ds.intrinsics(idx), dtype=np.float64)
+        mirrored = self.ds.flip_coins(idx, self.seed + epoch).astype(bool)
+        K[mirrored, 0, 2] = self.ds.resolution[0] + 1.0 - K[mirrored, 0, 2]
+        n = len(idx)
+        return K.reshape(n, 9).astype(np.float32), np.linalg.inv(K).reshape(n, 9).astype(np.float32)
 
     def __iter__(self):
         import torch
@@ -616,11 +661,19 @@ class DataLoader:
                                     x = (x, jitter(x, jitter.draw(cur, self.seed + epoch))) + extra
                                 elif extra:
                                     x = (x,) + extra
+                                if self.intrinsics:
+                                    kk = tuple(torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)
+                                               for a in self.batch_intrinsics(cur, epoch))
+                                    x = (x if isinstance(x, tuple) else (x,)) + kk
                                 ev = torch.cuda.Event()
                                 ev.record(stream)
                             q.put((x, ev, host))
                         else:
-                            q.put((host.to(dev) if dev is not None else host, None, None))
+                            x = host.to(dev) if dev is not None else host
+                            if self.intrinsics:
+                                x = (x,) + tuple(torch.from_numpy(a).to(dev) if dev is not None else torch.from_numpy(a)
+                                                 for a in self.batch_intrinsics(cur, epoch))
+                            q.put((x, None, None))
             except BaseException as e:            # surface decode errors in the consumer
                 q.put(e)
             finally:

@@ -83,18 +83,20 @@ class GradAllReduce:
 
 
 def train_step(executor, model, opt, x, comm: Optional[GradAllReduce] = None, loss=None, *,
-               x_stereo=None, stereo_Rt=None, temporal=True):
+               x_stereo=None, stereo_Rt=None, temporal=True, K=None, invK=None):
     """forward_loss -> backward segments (each followed by its bucket all-reduce) -> ADAM with
     gradient scale 1/world.  Returns the device loss tensor (this rank's shard loss).  A guarded
     ``opt`` (``ADAM(max_grad_norm=..., skip_nonfinite=...)``) measures, clips and skips on the reduced
     gradient, after the last bucket: every rank sees the same gradient and takes the same decision.
     ``x_stereo`` / ``stereo_Rt`` / ``temporal``: stereo supervision, as ``train_loss`` (this step composes
-    forward_loss with the segments, so it needs nothing of the C data-parallel step)."""
+    forward_loss with the segments, so it needs nothing of the C data-parallel step).
+    ``K`` / ``invK``: this rank's per-sample intrinsics, as ``train_loss``."""
     comm = comm or GradAllReduce()
     if x_stereo is None and (stereo_Rt is not None or not temporal):
         raise ValueError("stereo_Rt / temporal=False need x_stereo")
     stereo = {} if x_stereo is None else dict(x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal)
-    out = executor.forward_loss(x, None, loss=loss, **stereo)
+    intr = {} if K is None and invK is None else dict(K=K, invK=invK)
+    out = executor.forward_loss(x, None, loss=loss, **stereo, **intr)
     # one update after the last bucket unless MD2_SEG_UPDATE=1 (concurrent per-segment updates
     # measured 2% slower at N=1, profiles/r04_seg_update_ab.txt)
     # (and with a guarded optimiser: the gradient guard needs the whole reduced gradient)

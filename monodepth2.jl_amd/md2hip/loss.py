@@ -127,9 +127,39 @@ def check_stereo(x, x_stereo, stereo_Rt):
         raise ValueError("x must hold 3 frames")
 
 
+def check_intrinsics(K, invK, N, device):
+    """Per-sample intrinsics of a batch of N as the kernels read them: (K, invK), float32 [N, 9]
+    contiguous tensors on ``device``, or (None, None) when neither is given.  K / invK: float32
+    tensors on ``device``, [N,3,3] or [N,9].  K alone: invK is computed on the host in fp64 and
+    rounded once.  ValueError for a wrong type, shape, dtype or device, or invK without K."""
+    import torch
+    if K is None:
+        if invK is not None:
+            raise ValueError("invK needs K")
+        return None, None
+    out = []
+    for name, t in (("K", K), ("invK", invK)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
+        if tuple(t.shape) not in ((N, 3, 3), (N, 9)):
+            raise ValueError(f"{name} must have shape {(N, 3, 3)} or {(N, 9)}, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if t.device != torch.device(device):
+            raise ValueError(f"{name} is on {t.device}, x on {device}")
+        out.append(t.reshape(N, 9).contiguous())
+    if invK is None:
+        inv = np.linalg.inv(out[0].detach().cpu().numpy().astype(np.float64).reshape(N, 3, 3))
+        out.append(torch.from_numpy(inv.reshape(N, 9).astype(np.float32)).to(device))
+    return out[0], out[1]
+
+
 def stereo_sources(x, x_stereo, stereo_Rt, cache: TrainCache, temporal=True):
     """The ``md2_loss_source`` array of MS (temporal: the two temporal sources of ``cache``, learned,
     then the stereo frame, fixed -- Monodepth2's [0, -1, 1, "s"]) or of S (the stereo frame alone).
+    ``x_stereo`` None (with temporal): the two temporal sources alone, M in the sources form.
     Returns (array, nsrc, n_learned)."""
     N, L, C_, H, W = x.shape
     fs = C_ * H * W
@@ -144,6 +174,10 @@ def stereo_sources(x, x_stereo, stereo_Rt, cache: TrainCache, temporal=True):
         arr[s].invert = int(sid < cache.target_id)
         arr[s].Rt = None
     k = len(ids)
+    if x_stereo is None:
+        if not temporal:
+            raise ValueError("temporal=False needs x_stereo")
+        return arr, k, k
     arr[k].frames = x_stereo.data_ptr()
     arr[k].sample_stride = fs
     arr[k].pose_block = -1
@@ -185,7 +219,7 @@ def _results(disparities, x, nsrc, n_learned, grads, visualize):
 def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Params, *,
               grads=True, smooth_weights=None, divisor=None, smooth_normalize=True,
               dloss=1.0, sigmoid_grad=False, visualize=False, keep_workspace=False,
-              x_stereo=None, stereo_Rt=None, temporal=True):
+              x_stereo=None, stereo_Rt=None, temporal=True, K=None, invK=None):
     """The body of ``train_loss`` after the model call (src/training.jl:25-77) and its pullback.
 
     disparities: list of [N,1,h,w] float32 CUDA tensors (one per scale); poses: list of
@@ -201,11 +235,20 @@ def loss_tail(disparities, poses, x, auto_loss, cache: TrainCache, params: Param
     alone -- "S", ``temporal=False``, where ``poses`` is not read and d_pose is None.  The stereo
     transform is data: it gets no gradient.  vis_sel then holds 0..S-1 (the stereo frame last) or
     -1, vis_warped is [S,N,C,H,W] and vis_cell [nscales,S,N,H,W]; an ``auto_loss`` of None is
-    computed over the same sources."""
+    computed over the same sources.
+
+    Per-sample intrinsics: ``K`` (and optionally ``invK``) float32 device tensors [N,3,3] or [N,9];
+    sample i is warped by row i and cache.K / invK are not read (md2_loss_fwd_bwd_sources_k).  K
+    alone: invK is computed on the host in fp64 and rounded once.  The call then runs on the
+    kernel over sources whatever the number of sources; rows all equal to cache.K / invK give the
+    bits of the call without them."""
     import torch
-    if x_stereo is not None:
+    K, invK = check_intrinsics(K, invK, x.shape[0], x.device)
+    if x_stereo is not None or K is not None:
+        if x_stereo is None and (stereo_Rt is not None or not temporal):
+            raise ValueError("stereo_Rt / temporal=False need x_stereo")
         return _loss_tail_sources(disparities, poses, x, auto_loss, cache, params, x_stereo, stereo_Rt,
-                                  temporal, grads=grads, smooth_weights=smooth_weights, divisor=divisor,
+                                  temporal, K=K, invK=invK, grads=grads, smooth_weights=smooth_weights, divisor=divisor,
                                   smooth_normalize=smooth_normalize, dloss=dloss, sigmoid_grad=sigmoid_grad,
                                   visualize=visualize, keep_workspace=keep_workspace)
     if stereo_Rt is not None or not temporal:
@@ -248,12 +291,14 @@ def _sources_cfg(N, C_, W, H, shapes, cache, params, **kw):
 def run_loss_sources(disparities, pose, x, target, target_stride, sources, nsrc, n_learned, auto_loss,
                      cache, params, *, grads=True, smooth_weights=None, divisor=None,
                      smooth_normalize=True, dloss=1.0, sigmoid_grad=False, visualize=False,
-                     keep_workspace=False):
+                     keep_workspace=False, K=None, invK=None):
     """md2_loss_fwd_bwd_sources on an ``md2_loss_source`` array (``stereo_sources``; the tests build
-    their own).  x only gives the shape [N,L,C,H,W] and the device; target is a device address."""
+    their own).  x only gives the shape [N,L,C,H,W] and the device; target is a device address.
+    ``K`` / ``invK`` (``check_intrinsics``): per-sample intrinsics, md2_loss_fwd_bwd_sources_k."""
     import torch
     N, L, C_, H, W = x.shape
     dev = x.device
+    K, invK = check_intrinsics(K, invK, N, dev)
     for d in disparities:
         assert d.dtype == torch.float32 and d.is_contiguous() and d.device == dev
     shapes = [(d.shape[-2], d.shape[-1]) for d in disparities]
@@ -276,6 +321,12 @@ def run_loss_sources(disparities, pose, x, target, target_stride, sources, nsrc,
             if tuple(am.shape) != (N, 1, H, W) or am.dtype != torch.float32 or am.device != dev:
                 raise ValueError(f"auto_loss must be float32 [N,1,H,W] = {(N, 1, H, W)} on {dev}")
     disp_arr = ptr_array(disparities)
+    if K is not None:
+        check(lib().md2_loss_fwd_bwd_sources_k(C.byref(cfg), nsrc, sources, C.c_void_p(target), target_stride,
+                                               ptr(K), ptr(invK), C.cast(disp_arr, _lib.FP), ptr(pose), ptr(am),
+                                               C.c_float(dloss), C.byref(out), ptr(ws), stream_of(dev)),
+              "md2_loss_fwd_bwd_sources_k")
+        return res
     check(lib().md2_loss_fwd_bwd_sources(C.byref(cfg), nsrc, sources, C.c_void_p(target), target_stride,
                                          C.cast(disp_arr, _lib.FP), ptr(pose), ptr(am), C.c_float(dloss),
                                          C.byref(out), ptr(ws), stream_of(dev)),
@@ -286,7 +337,8 @@ def run_loss_sources(disparities, pose, x, target, target_stride, sources, nsrc,
 def _loss_tail_sources(disparities, poses, x, auto_loss, cache, params, x_stereo, stereo_Rt, temporal, **kw):
     import torch
     assert x.dtype == torch.float32 and x.is_contiguous()
-    check_stereo(x, x_stereo, stereo_Rt)
+    if x_stereo is not None:
+        check_stereo(x, x_stereo, stereo_Rt)
     N, L, C_, H, W = x.shape
     sources, nsrc, n_learned = stereo_sources(x, x_stereo, stereo_Rt, cache, temporal)
     pose = pack_poses(poses).to(x.device, torch.float32) if temporal else None

@@ -144,6 +144,7 @@ class _Executor:
     """One libmd2hip model instance (activations/workspace) for a fixed problem size."""
 
     _guard = (False, None)                  # the library's gradient-guard (on, max_norm) of this executor
+    _intr = None                            # the (K, invK) [batch, 9] tensors set in the library, or None
 
     def __init__(self, model: "Model", batch, height, width, cache: TrainCache, params: Params,
                  num_bins: int = 32):
@@ -270,6 +271,23 @@ class _Executor:
               "md2_model_set_disparity_bins")
         self._bins = b                       # the copy is async: keep the source alive
 
+    def set_intrinsics(self, K=None, invK=None, device=None):
+        """Per-sample intrinsics of the following forward_loss / train_step_graph calls
+        (md2_model_set_intrinsics): float32 device tensors [batch,3,3] or [batch,9]
+        (``md2hip.loss.check_intrinsics``; K alone: invK from an fp64 inverse on the host).  None
+        returns to TrainCache.K.  The public calls pass their ``K=`` / ``invK=`` here on every call."""
+        if K is None and invK is None:       # the plain call: nothing to do unless they were set
+            if self._intr is not None:
+                check(lib().md2_model_set_intrinsics(self.handle, None, None, stream_of(self.model.device)),
+                      "md2_model_set_intrinsics")
+                self._intr = None
+            return
+        from .loss import check_intrinsics
+        Kd, iKd = check_intrinsics(K, invK, self.batch, self.model.flat.device if device is None else device)
+        check(lib().md2_model_set_intrinsics(self.handle, ptr(Kd), ptr(iKd), stream_of(self.model.device)),
+              "md2_model_set_intrinsics")
+        self._intr = (Kd, iKd)               # the copy is async: keep the sources alive
+
     def _check_net(self, x, x_net):
         import torch
         if (tuple(x_net.shape) != tuple(x.shape) or x_net.dtype != torch.float32 or x_net.device != x.device
@@ -286,17 +304,20 @@ class _Executor:
         return True
 
     def forward_loss(self, x, auto_loss=None, loss=None, terms=None, x_net=None, x_stereo=None,
-                     stereo_Rt=None, temporal=True):
+                     stereo_Rt=None, temporal=True, K=None, invK=None):
         """``x_net`` (like x, e.g. ``color_jitter(x, ...)``): the frames the networks see; the automask
         and the loss tail read x (md2_model_forward_loss_aug).  None: the plain call.
         ``x_stereo`` [N,C,H,W] with ``stereo_Rt`` [N,12] (``stereo_transforms``): stereo supervision
         (md2_model_forward_loss_stereo) -- ``temporal=True`` "MS", the loss over both temporal sources
         and the stereo frame; ``temporal=False`` "S", the stereo frame alone (the pose network's
-        gradient is then zero).  Only the loss and the automask read the stereo frame."""
+        gradient is then zero).  Only the loss and the automask read the stereo frame.
+        ``K`` / ``invK``: per-sample intrinsics of THIS call (``set_intrinsics``); without them the
+        loss warps every sample with TrainCache.K."""
         import torch
         self.model._require_train("train_loss / forward_loss")
         loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=x.device)
         self.sync()
+        self.set_intrinsics(K, invK, x.device)
         am = auto_loss.contiguous() if (self.automask and auto_loss is not None) else None
         if self._check_stereo(x, x_stereo, stereo_Rt, temporal):
             if x_net is not None:
@@ -347,8 +368,9 @@ class _Executor:
         self.cotangents = True
 
     def train_step_graph(self, x, opt: "ADAM", auto_loss=None, loss=None, x_net=None, x_stereo=None,
-                         stereo_Rt=None, temporal=True):
-        """``x_stereo`` / ``stereo_Rt`` / ``temporal`` as for ``forward_loss``
+                         stereo_Rt=None, temporal=True, K=None, invK=None):
+        """``K`` / ``invK``: per-sample intrinsics of this call, as for ``forward_loss``; the step is
+        captured again when they come or go, not when their values change.  ``x_stereo`` / ``stereo_Rt`` / ``temporal`` as for ``forward_loss``
         (md2_model_train_step_graph_stereo; captured again when the presence of the stereo source or
         ``temporal`` changes).  One full step (forward, loss, backward, Flux ADAM with opt's state) replayed as a
         captured hipGraph (md2_model_train_step_graph): the same kernels in the same order as
@@ -361,6 +383,7 @@ class _Executor:
             raise NotImplementedError("the captured step uses ADAM's defaults beta=(0.9, 0.999), eps=1e-8")
         loss = loss if loss is not None else torch.empty(1, dtype=torch.float32, device=x.device)
         self.sync()
+        self.set_intrinsics(K, invK, x.device)
         if opt.m is None:
             opt.m = torch.zeros_like(self.model.flat)
             opt.v = torch.zeros_like(self.model.flat)
@@ -615,7 +638,7 @@ def disparity_bins(batch: int, num_bins: int, u=None, device="cuda", near=1.0, f
 
 def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
                do_visualization: bool = False, num_bins: int = 32, bins=None, x_net=None, x_stereo=None,
-               stereo_Rt=None, temporal=True):
+               stereo_Rt=None, temporal=True, K=None, invK=None):
     """``train_loss(model, x, auto_loss, cache, params, do_visualization)`` (src/training.jl:21).
     Runs the forward and the fused loss-tail pullback; call ``gradient(model)`` for the rest of
     the backward.  Returns (loss, vis_disparity, vis_warped, vis_loss).  MPI mode (the model's
@@ -627,12 +650,16 @@ def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
     stereo), Monodepth2's [0, -1, 1, "s"]) or "S" (``temporal=False``: the stereo frame alone; the pose
     network still runs and gets a zero gradient).  The networks never see the stereo frame; with
     ``auto_loss=None`` the automask is taken over the same sources as the loss.  vis_warped then has
-    one entry per source."""
+    one entry per source.  ``K`` / ``invK`` (float32 device tensors [N,3,3] or [N,9]; not in MPI
+    mode): per-sample intrinsics of this call -- sample i is warped by row i instead of cache.K, as a
+    batch chained from datasets with different cameras or mirrored by ``FlipX`` needs
+    (``DataLoader(..., intrinsics=True)`` yields them).  K alone: invK from an fp64 host inverse."""
     model._require_train("train_loss")
     ex = model.executor(tuple(x.shape), cache, params, num_bins)
     if ex.emb:
         ex.set_bins(disparity_bins(x.shape[0], num_bins, device=x.device) if bins is None else bins)
-    loss = ex.forward_loss(x, auto_loss, x_net=x_net, x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal)
+    loss = ex.forward_loss(x, auto_loss, x_net=x_net, x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal,
+                           K=K, invK=invK)
     if not do_visualization:
         return loss, None, None, None
     # training.jl:34-37,71-74: the last disparity, both warped sources and the per-pixel warp
@@ -652,7 +679,8 @@ def train_loss(model: Model, x, auto_loss, cache: TrainCache, params: Params,
                     Params(target_size=params.target_size, batch_size=N * nb, min_depth=params.min_depth,
                            max_depth=params.max_depth, disparity_smoothness=params.disparity_smoothness,
                            automasking=params.automasking), grads=False, visualize=True,
-                    x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal)
+                    x_stereo=x_stereo, stereo_Rt=stereo_Rt, temporal=temporal,
+                    K=None if K is None else ex._intr[0], invK=None if K is None else ex._intr[1])
     return (loss, disps[-1].cpu(), [w.cpu() for w in vis["vis_warped"].unbind(0)],
             vis["vis_loss"][-1].unsqueeze(1).cpu())
 
@@ -841,12 +869,12 @@ class ADAM:
 
 
 def train_step(model: Model, x, auto_loss, cache: TrainCache, params: Params, opt: ADAM, x_net=None,
-               x_stereo=None, stereo_Rt=None, temporal=True):
+               x_stereo=None, stereo_Rt=None, temporal=True, K=None, invK=None):
     """One ``gradient(θ) do train_loss(...)[1] end`` + ``update!`` on one GPU (``x_net``, ``x_stereo``,
-    ``stereo_Rt``, ``temporal``: see ``train_loss``)."""
+    ``stereo_Rt``, ``temporal``, ``K``, ``invK``: see ``train_loss``)."""
     model._require_train("train_step")
     loss, *_ = train_loss(model, x, auto_loss, cache, params, x_net=x_net, x_stereo=x_stereo,
-                          stereo_Rt=stereo_Rt, temporal=temporal)
+                          stereo_Rt=stereo_Rt, temporal=temporal, K=K, invK=invK)
     gradient(model)
     opt.update(model)
     return loss
