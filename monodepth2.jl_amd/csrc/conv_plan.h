@@ -8,17 +8,34 @@ namespace md2 {
 
 constexpr int TARGET_BLOCKS = 1536;  // ~6 blocks (waves per SIMD) per CU on 256 CUs
 
-// T128x64q: 128x64 with the 4 waves stacked along M (each 32 rows x 64 columns: its A rows are its
-// own, B shared through LDS)
-enum TileCfg { T128x128 = 0, T64x256 = 1, T32x256 = 2, T64x128 = 3, T128x64 = 4, T64x64 = 5, T32x128 = 6,
-               T128x64q = 7 };
-const int TILE_BM[] = {128, 64, 32, 64, 128, 64, 32, 128};
-const int TILE_BN[] = {128, 256, 256, 128, 64, 64, 128, 64};
+// The tiles the tile kernels are built for, each stated once.  The enum, the BM / BN lookups and
+// the launchers' dispatch (launch_px, launch_w_tile) are generated from these lists: a tile the
+// planner can name has a launcher case, and no kernel is built for a tile it cannot name.
+// fwd / dgrad: X(name, BM, BN, WM, WN), BM x BN outputs on 4 waves as WM x WN.  64x64 where M > 32,
+// 32x128 below (plan_px, with the measurements against larger tiles).
+#define MD2_PX_TILES(X) X(T64x64, 64, 64, 2, 2) X(T32x128, 32, 128, 1, 4)
+// wgrad: X(name, BM, BN, WM, WN, id); columns are tap-major (tap groups x CW channels).  id is the
+// number MD2_W_TILE takes (1 was a 32x256 tile; 4 and 5 are the two routes below)
+#define MD2_W_TILES(X) \
+  X(W64x128, 64, 128, 2, 2, 0) X(W64x64, 64, 64, 2, 2, 2) X(W32x128, 32, 128, 1, 4, 3) X(W64x192, 64, 192, 2, 2, 6)
 
-// wgrad tiles (BM x BN, 4 waves as WM x WN); columns are tap-major (tap groups x CW channels)
-enum WTileCfg { W64x128 = 0, W32x256 = 1, W64x64 = 2, W32x128 = 3, W16x144 = 4, WSTEM = 5, W64x192 = 6 };
-const int WT_BM[] = {64, 32, 64, 32, 16, 64, 64};
-const int WT_BN[] = {128, 256, 64, 128, 144, 64, 192};
+#define MD2_TILE_ENUM(name, ...) name,
+#define MD2_W_TILE_ENUM(name, BM, BN, WM, WN, id) name = id,
+enum TileCfg { MD2_PX_TILES(MD2_TILE_ENUM) };
+// W16x144 and WSTEM: routes with kernels of their own (conv_wgrad16_kernel, conv_wgrad_stem_kernel)
+enum WTileCfg { MD2_W_TILES(MD2_W_TILE_ENUM) W16x144 = 4, WSTEM = 5 };
+#undef MD2_TILE_ENUM
+#undef MD2_W_TILE_ENUM
+
+// BM / BN of a tile of the lists; 0: not a built tile
+#define MD2_TILE_BM(name, BM, ...) case name: return BM;
+#define MD2_TILE_BN(name, BM, BN, ...) case name: return BN;
+constexpr int TILE_BM(int tile) { switch (tile) { MD2_PX_TILES(MD2_TILE_BM) default: return 0; } }
+constexpr int TILE_BN(int tile) { switch (tile) { MD2_PX_TILES(MD2_TILE_BN) default: return 0; } }
+constexpr int WT_BM(int tile) { switch (tile) { MD2_W_TILES(MD2_TILE_BM) default: return 0; } }
+constexpr int WT_BN(int tile) { switch (tile) { MD2_W_TILES(MD2_TILE_BN) default: return 0; } }
+#undef MD2_TILE_BM
+#undef MD2_TILE_BN
 
 // (KH, S, RFL) combos instantiated
 #define MD2_CONV_COMBOS(X) X(1, 1, 0) X(1, 2, 0) X(3, 1, 0) X(3, 1, 1) X(3, 2, 0) X(7, 2, 0)

@@ -149,16 +149,11 @@ int launch_px16(const ConvShape& s, ConvArgs& a, hipStream_t st) {
   conv_arith_ref() = 1;
   conv_note_kernel("px16");
   a.g.kper = (int)round_up(a.g.K, 16);
-  static const int bn = tuning_knob("MD2_PX16_BN", 128);   // 128 measured faster on every decoder shape
-  const bool big = bn == 256;
-  const dim3 grid(cdiv(a.g.N, big ? 256 : 128));
+  const dim3 grid(cdiv(a.g.N, 128));
 #define MD2_P16_CASE(KS, SS, RR)                                                                 \
   if constexpr (SS == 1) {                                                                       \
     if (s.KH == KS && s.stride == SS && s.reflect == RR) {                                       \
-      if (big)                                                                                   \
-        hipLaunchKernelGGL((conv_px16_kernel<MODE, 256, KS, KS, SS, RR>), grid, dim3(256), 0, st, a); \
-      else                                                                                       \
-        hipLaunchKernelGGL((conv_px16_kernel<MODE, 128, KS, KS, SS, RR>), grid, dim3(256), 0, st, a); \
+      hipLaunchKernelGGL((conv_px16_kernel<MODE, 128, KS, KS, SS, RR>), grid, dim3(256), 0, st, a); \
       MD2_LAUNCH_CHECK();                                                                        \
       return MD2_OK;                                                                             \
     }                                                                                            \
@@ -213,14 +208,13 @@ int launch_px(const ConvShape& s, ConvArgs& a, const PxRoute& r, const Plan& til
       defer->stats_parts = (int)cdiv(a.g.N, 256);
     }
   } else switch (p.tile) {
-    case T128x128: rc = launch_px_tile<MODE, 128, 128, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
-    case T64x256: rc = launch_px_tile<MODE, 64, 256, 1, 4>(s, a, r.arith, tap, p.BK, grid, st); break;
-    case T64x128: rc = launch_px_tile<MODE, 64, 128, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
-    case T128x64: rc = launch_px_tile<MODE, 128, 64, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
-    case T64x64: rc = launch_px_tile<MODE, 64, 64, 2, 2>(s, a, r.arith, tap, p.BK, grid, st); break;
-    case T32x128: rc = launch_px_tile<MODE, 32, 128, 1, 4>(s, a, r.arith, tap, p.BK, grid, st); break;
-    case T128x64q: rc = launch_px_tile<MODE, 128, 64, 4, 1>(s, a, r.arith, tap, p.BK, grid, st); break;
-    default: rc = launch_px_tile<MODE, 32, 256, 1, 4>(s, a, r.arith, tap, p.BK, grid, st); break;
+#define MD2_PX_TILE_CASE(NAME, BM, BN, WM, WN) \
+    case NAME: rc = launch_px_tile<MODE, BM, BN, WM, WN>(s, a, r.arith, tap, p.BK, grid, st); break;
+    MD2_PX_TILES(MD2_PX_TILE_CASE)
+#undef MD2_PX_TILE_CASE
+    default:
+      set_error("conv: the plan names a tile that has no launcher");
+      return MD2_EINVAL;
   }
   if (rc) return rc;
   const TensorOut& o = a.out;

@@ -11,20 +11,18 @@ namespace md2 {
 // tile selection, split-K planning (conv_plan.h)
 // ---------------------------------------------------------------------------------------------
 // debugging / tuning overrides of the planner (read once; honoured only under MD2_TUNING=1,
-// common.h tuning_knob): MD2_PX_TILE=<TileCfg>, MD2_PX_TARGET=<target blocks for split-K>, ...
+// common.h tuning_knob): MD2_PX_TARGET=<target blocks for split-K>, MD2_PX_BK=<16 | 32>, ...
 static Plan plan_px(int M, long N, int K, bool bk32_ok = false, bool prefer32 = false) {
   // Small tiles, many blocks: at B=12 the GEMMs are ~0.5 chip of 128x128 tiles; 64x64 tiles
   // (30 VGPR + 16 AGPR, 8 waves/SIMD) with ~1536 blocks keep 4-6 waves per SIMD in flight and
-  // ran 10-50% faster than 128x128 / 64x256 on every encoder shape (tools/sweep_px.sh, r01).
-  static const int tile_override = tuning_knob("MD2_PX_TILE", -1);
+  // ran 10-50% faster than 128x128 / 64x256 on every encoder shape (r01); 64x128 / 64x256 /
+  // 128x64 under the bf16 split-product kernel 5-17% slower again (profiles/r04_sweep_px3.txt).
+  // The two tiles below are the ones built (conv_plan.h, MD2_PX_TILES).
   static const int target = tuning_knob("MD2_PX_TARGET", TARGET_BLOCKS);
   Plan p{};
   p.tile = M > 32 ? T64x64 : T32x128;
-  if (tile_override >= 0 && tile_override <= T128x64q &&
-      ((M > 32 && TILE_BM[tile_override] >= 64) || (M <= 32 && TILE_BM[tile_override] == 32)))
-    p.tile = tile_override;
-  p.BM = TILE_BM[p.tile];
-  p.BN = TILE_BN[p.tile];
+  p.BM = TILE_BM(p.tile);
+  p.BN = TILE_BN(p.tile);
   static const int bk_override = tuning_knob("MD2_PX_BK", 0);
   p.BK = ((bk_override == 32 || (prefer32 && bk_override != 16)) && bk32_ok) ? 32 : 16;
   if (K <= 0) {                // a parity class without taps: the kernel only writes zeros
@@ -268,9 +266,9 @@ static WPlan plan_wgrad(const ConvShape& s, int c0, bool tap) {
   const int M = s.Cout;
   const int KK = s.KH * s.KW;
   auto ntiles = [&](int tile, int& cw) {
-    cw = tap ? wgrad_cw(s, c0, WT_BN[tile]) : 0;
-    const long nt = cw ? (long)cdiv(KK, WT_BN[tile] / cw) * (s.Cin / cw) : cdiv((long)s.Cin * KK, WT_BN[tile]);
-    return (long)cdiv(M, WT_BM[tile]) * nt;
+    cw = tap ? wgrad_cw(s, c0, WT_BN(tile)) : 0;
+    const long nt = cw ? (long)cdiv(KK, WT_BN(tile) / cw) * (s.Cin / cw) : cdiv((long)s.Cin * KK, WT_BN(tile));
+    return (long)cdiv(M, WT_BM(tile)) * nt;
   };
   // M <= 32: 32x128 (1024 blocks); else 64x128 with split-K to ~512 blocks, or 64x64 when the
   // grid is already >= 256 tiles without splitting (tools/sweep_w.sh, r01)
@@ -300,10 +298,10 @@ static WPlan plan_wgrad(const ConvShape& s, int c0, bool tap) {
   if (w192 && p.tile == W64x128 && KK == 9 && tap && wgrad_cw(s, c0, 128) == 64 &&
       wgrad_cw(s, c0, 192) == 64)
     p.tile = W64x192;
-  if (tile_override >= 0 && tile_override <= W32x128) p.tile = tile_override;
+  if (WT_BM(tile_override)) p.tile = tile_override;   // the number of a built tile (conv_plan.h); others: ignored
   if (target > 0) tgt = target;
-  p.BM = WT_BM[p.tile];
-  p.BN = WT_BN[p.tile];
+  p.BM = WT_BM(p.tile);
+  p.BN = WT_BN(p.tile);
   const long tiles = ntiles(p.tile, p.cw);
   p.ntiles_n = tiles / cdiv(M, p.BM);
   const long K = (long)s.N * s.Ho * s.Wo;

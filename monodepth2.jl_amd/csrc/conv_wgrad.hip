@@ -64,21 +64,33 @@ void launch_w_cw(const ConvArgs& a, dim3 grid, hipStream_t st) {
 
 template <int BM, int BN, int WM, int WN, int KS, int SS, int RR>
 int launch_w(int cw, const ConvArgs& a, dim3 grid, hipStream_t st) {
-  switch (cw) {
-    case 0:
-      conv_arith_ref() = 1;
-      conv_note_kernel("wgrad_tile", BM, BN, 0);
-      hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, 32, WM, WN, KS, KS, SS, RR>), grid, dim3(256), 0,
-                         st, a);
-      break;
-    case 16: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 16>(a, grid, st); break;
-    case 32: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 32>(a, grid, st); break;
-    case 64: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 64>(a, grid, st); break;
-    case 128: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 128>(a, grid, st); break;
-    default: return MD2_ENOTSUP;
+  if constexpr (BN == 192) {
+    // three 64-channel taps per column tile: the 3x3 convs' 64-channel tap blocks only
+    if constexpr (KS == 3) {
+      if (cw == 64) {
+        launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 64>(a, grid, st);
+        MD2_LAUNCH_CHECK();
+        return MD2_OK;
+      }
+    }
+    return MD2_ENOTSUP;
+  } else {
+    switch (cw) {
+      case 0:
+        conv_arith_ref() = 1;
+        conv_note_kernel("wgrad_tile", BM, BN, 0);
+        hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, 32, WM, WN, KS, KS, SS, RR>), grid, dim3(256), 0,
+                           st, a);
+        break;
+      case 16: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 16>(a, grid, st); break;
+      case 32: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 32>(a, grid, st); break;
+      case 64: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 64>(a, grid, st); break;
+      case 128: launch_w_cw<BM, BN, WM, WN, KS, SS, RR, 128>(a, grid, st); break;
+      default: return MD2_ENOTSUP;
+    }
+    MD2_LAUNCH_CHECK();
+    return MD2_OK;
   }
-  MD2_LAUNCH_CHECK();
-  return MD2_OK;
 }
 
 // W_HEAD: the batched kernel where this call's alignment and store mode fit it
@@ -98,27 +110,23 @@ static int wgrad_head(const ConvShape& s, const TensorIn& x, const float* dy, fl
   return head_wgrad(j, s.reflect, accumulate, ws.ptr, ws.bytes, st);
 }
 
-// W_TILE: the generic tiles of the plan
+// W_TILE: the generic tiles of the plan (conv_plan.h, MD2_W_TILES: one case per built tile)
 static int launch_w_tile(const ConvShape& s, const WPlan& p, const ConvArgs& a, dim3 grid, hipStream_t st) {
-#define MD2_W_CASE(KS, SS, RR)                                                                     \
-  if (s.KH == KS && s.stride == SS && s.reflect == RR) {                                           \
+#define MD2_W_TILE_CASE(NAME, BM, BN, WM, WN, ID) \
+  case NAME: return launch_w<BM, BN, WM, WN, KS, SS, RR>(p.cw, a, grid, st);
+#define MD2_W_CASE(KS_, SS_, RR_)                                                                  \
+  if (s.KH == KS_ && s.stride == SS_ && s.reflect == RR_) {                                        \
+    constexpr int KS = KS_, SS = SS_, RR = RR_;                                                    \
     switch (p.tile) {                                                                              \
-      case W32x256: return launch_w<32, 256, 1, 4, KS, SS, RR>(p.cw, a, grid, st);                 \
-      case W64x64: return launch_w<64, 64, 2, 2, KS, SS, RR>(p.cw, a, grid, st);                   \
-      case W32x128: return launch_w<32, 128, 1, 4, KS, SS, RR>(p.cw, a, grid, st);                 \
-      case W64x192:                                                                                \
-        if constexpr (KS == 3) {                                                                   \
-          if (p.cw == 64) {                                                                        \
-            launch_w_cw<64, 192, 2, 2, KS, SS, RR, 64>(a, grid, st);                               \
-            return MD2_OK;                                                                         \
-          }                                                                                        \
-        }                                                                                          \
-        return MD2_ENOTSUP;                                                                        \
-      default: return launch_w<64, 128, 2, 2, KS, SS, RR>(p.cw, a, grid, st);                      \
+      MD2_W_TILES(MD2_W_TILE_CASE)                                                                 \
+      default:                                                                                     \
+        set_error("conv_wgrad: the plan names a tile that has no launcher");                       \
+        return MD2_EINVAL;                                                                         \
     }                                                                                              \
   }
   MD2_CONV_COMBOS(MD2_W_CASE)
 #undef MD2_W_CASE
+#undef MD2_W_TILE_CASE
   return MD2_ENOTSUP;
 }
 
